@@ -13,6 +13,13 @@ timed steps bracketed by barrier + torch.cuda.synchronize on both sides;
 elapsed = MAX over ranks; rank 0 prints one JSON line.
 
 Weak scaling: per-GPU batch is fixed (16) as N grows.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line. ``--dump-outputs DIR`` additionally
+writes what the last timed step computed as DIR/<name>.npy (float32) so two
+builds can be compared output for output; the inputs and the initial weights
+are seeded, hence identical from run to run. ``--full`` is reserved for any
+extra measurement or check beyond the headline (there is none today).
 """
 
 import argparse
@@ -54,6 +61,13 @@ def build_args():
                    action='store_true', default=True)
     p.add_argument('--no-channels-last', dest='channels_last',
                    action='store_false')
+    p.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed '
+                        'step computed as DIR/<name>.npy (float32)')
+    p.add_argument('--full', action='store_true', default=False,
+                   help='also run every measurement and check beyond the '
+                        'headline figure (none today: the plain run is '
+                        'already only the headline)')
     return p.parse_args()
 
 
@@ -69,6 +83,31 @@ def make_synthetic_batches(batch_size, imsize, device, n_batches=2, seed=777):
         img, hm, off, wh, mask, _ = ds.collate_fn(items)
         batches.append(tuple(t.to(device) for t in (img, hm, off, wh, mask)))
     return batches
+
+
+# --dump-outputs writes at most this much in all
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_SAMPLE_SEED = 2028
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor} as dirname/<name>.npy in float32. Small arrays
+    are written whole; one that does not fit its share of what is left of
+    the budget is replaced by a fixed, seeded sample of its flattened
+    elements (same indices on every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for n, (name, t) in enumerate(todo):
+        a = t.detach().to('cpu', torch.float32).contiguous().numpy()
+        share = left // (len(todo) - n)
+        if a.size > share:
+            rng = np.random.RandomState(DUMP_SAMPLE_SEED)
+            idx = np.sort(rng.randint(0, a.size, size=share))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def main():
@@ -130,6 +169,13 @@ def main():
     calc = LossCalculator().to(device)
     is_bucketed = world > 1
 
+    # --dump-outputs: what the step on batch slot b last returned. Under
+    # hipGraph these are the graph's static output tensors, refreshed by
+    # every replay and taken from the capture's return value as
+    # engine/graphed.py does. Nothing is kept on a run without the option.
+    keep = args.dump_outputs is not None
+    kept = {}
+
     graph_active = False
     if args.mode == 'train':
         # N>1 captures the bucketed RCCL all-reduce into the graph too
@@ -154,6 +200,7 @@ def main():
                 model.finish_backward()
             opt.step()
             opt.zero_grad(set_to_none=True)
+            return out.detach(), total.detach()
 
         step = eager_step
         if want_graph:
@@ -172,8 +219,11 @@ def main():
                     # must not invalidate an N>1 capture
                     with torch.cuda.graph(
                             g, capture_error_mode='thread_local'):
-                        eager_step(b)
+                        res = eager_step(b)
                     graphs.append(g)
+                    if keep:
+                        kept[b] = res
+                    del res
                 calc._pending.clear()
 
                 def step(i):
@@ -194,18 +244,24 @@ def main():
 
             def step(i):
                 img = batches[i % len(batches)][0]
-                predictor(img)
+                return predictor(img)
         elif args.fp8 and use_cuda:
             def step(i):
                 img = batches[i % len(batches)][0]
                 with rthd_amp.autocast(enabled=amp_on), \
                         rthd_amp.fp8_autocast(True), torch.no_grad():
-                    predictor(img)
+                    return predictor(img)
         else:
             def step(i):
                 img = batches[i % len(batches)][0]
                 with rthd_amp.autocast(enabled=amp_on), torch.no_grad():
-                    predictor(img)
+                    return predictor(img)
+
+    if keep and not graph_active:
+        inner_step = step
+
+        def step(i):
+            kept[i % len(batches)] = inner_step(i)
 
     def barrier_sync():
         if dist is not None and world > 1:
@@ -234,7 +290,32 @@ def main():
     n_gpus = world if env_launched else (1 if use_cuda else 1)
     total_imgs = args.batch_size * n_gpus * args.steps
     value = total_imgs / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
+    ms_per_step = elapsed / max(args.steps, 1) * 1e3
+
+    if keep and rank == 0 and args.steps > 0:
+        last = kept[(args.steps - 1) % len(batches)]
+        if args.mode == 'train':
+            # what a training step hands back: the network's logits, the
+            # summed loss, and the parameters as the optimizer left them
+            arrays = {
+                'outputs': last[0],
+                'loss': last[1].reshape(1),
+                'params': torch.cat([p.detach().reshape(-1).float()
+                                     for p in net.parameters()]),
+            }
+        else:
+            # per-image detection lists, concatenated; counts splits them
+            box_lst, cls_lst, score_lst = last
+            arrays = {
+                'boxes': torch.cat([b.reshape(-1, 4) for b in box_lst]),
+                'classes': torch.cat([c.reshape(-1) for c in cls_lst]),
+                'scores': torch.cat([s.reshape(-1) for s in score_lst]),
+                'counts': torch.tensor([len(s) for s in score_lst]),
+            }
+        dump_outputs(args.dump_outputs, arrays)
+        del last, arrays
+    # drop the kept outputs before the graphs that own their memory go
+    kept.clear()
 
     if rank == 0:
         result = {

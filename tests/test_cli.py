@@ -1,6 +1,7 @@
 """CLI-contract tests: the reference's main.py / export.py / evaluate.py
 entry points run end to end as subprocesses (reference main.py:9-17,
-export.py:99-130, evaluate.py:245-290). Tiny synthetic configs on CPU."""
+export.py:99-130, evaluate.py:245-290), and bench.py's result line and
+--dump-outputs. Tiny synthetic configs on CPU."""
 
 import os
 import subprocess
@@ -69,6 +70,64 @@ def test_export_cli(tmp_path):
     assert len(out) == 3
 
 
+BENCH_FLAGS = [
+    '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch-size', '2',
+    '--imsize', '64', '--hourglass-inch', '16',
+]
+
+
+def _run_bench(extra, cwd):
+    """bench.py on CPU (devices hidden from the child); returns the parsed
+    result line."""
+    import json
+    env = dict(os.environ)
+    env['PYTHONPATH'] = REPO
+    env['CUDA_VISIBLE_DEVICES'] = ''
+    env['HIP_VISIBLE_DEVICES'] = ''
+    r = subprocess.run(
+        [sys.executable, os.path.join(REPO, 'bench.py')] + BENCH_FLAGS +
+        extra, cwd=cwd, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_cli_dump_outputs(tmp_path):
+    """bench.py contract: one JSON result line whose steps/ms_per_step
+    follow --steps, --full accepted, and --dump-outputs writes the last
+    timed step's arrays as float32 .npy, identical from run to run."""
+    import numpy as np
+    res = _run_bench(['--full', '--dump-outputs', str(tmp_path / 'a')],
+                     cwd=str(tmp_path))
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype',
+              'ms_per_step'):
+        assert k in res, k
+    assert res['steps'] == 3 and res['warmup'] == 1
+    assert res['metric'] == 'train imgs/sec' and res['unit'] == 'imgs/sec'
+    assert res['ms_per_step'] > 0
+    # value = batch * steps / elapsed and ms_per_step = elapsed / steps
+    assert res['value'] == pytest.approx(2 * 1e3 / res['ms_per_step'],
+                                         rel=1e-2)
+
+    _run_bench(['--dump-outputs', str(tmp_path / 'b')], cwd=str(tmp_path))
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['loss.npy', 'outputs.npy', 'params.npy']
+    assert sorted(os.listdir(tmp_path / 'b')) == names
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / 'a' / n)
+        b = np.load(tmp_path / 'b' / n)
+        assert a.dtype == np.float32
+        assert np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / 'a' / 'outputs.npy').shape == (2, 1, 6, 16, 16)
+    # nothing but the dump directories is written next to the run
+    assert sorted(os.listdir(tmp_path)) == ['a', 'b']
+
+
 def test_main_train_torchrun_2rank(tmp_path):
     """The exact multi-rank CLI path the 8-GPU run uses: torchrun launches
     main.py --train-flag, one worker per rank (gloo on CPU), bucketed
@@ -76,6 +135,10 @@ def test_main_train_torchrun_2rank(tmp_path):
     env = dict(os.environ)
     env['PYTHONPATH'] = REPO
     env.setdefault('MASTER_ADDR', '127.0.0.1')
+    # CPU workers rendezvous over gloo; with a GPU visible the launcher
+    # would pick nccl for them, so hide the devices from the children
+    env['CUDA_VISIBLE_DEVICES'] = ''
+    env['HIP_VISIBLE_DEVICES'] = ''
     r = subprocess.run(
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
          '--nproc-per-node', '2', '--master-addr', '127.0.0.1',

@@ -21,6 +21,16 @@ def rel_err(got, want):
             want.abs().max().clamp(min=1e-6)).item()
 
 
+def _zero_grad_names(ref64, x, dy):
+    """Names of the parameters whose gradient is analytically zero (a conv
+    bias under train-mode BN), found on a float64 copy of the module: there
+    the summation residue is ~1e-13, whereas in float32 it is ~1e-4 and
+    moves across that size with the number of CPU threads."""
+    ref64(x.double()).backward(dy.double())
+    return {name for name, p in ref64.named_parameters()
+            if p.grad is not None and p.grad.abs().max() < 1e-9}
+
+
 def _run_pair(make_module, x_shape, seed, train=True, x_grad=True):
     """Run fwd+bwd of the same module CPU-eager vs GPU-f32 and return
     (cpu_module, gpu_module, cpu_x, gpu_x, cpu_y, gpu_y)."""
@@ -36,11 +46,13 @@ def _run_pair(make_module, x_shape, seed, train=True, x_grad=True):
     g = torch.Generator().manual_seed(seed + 1)
     x = torch.randn(*x_shape, generator=g)
     dy_gen = torch.Generator().manual_seed(seed + 2)
+    ref64 = copy.deepcopy(cpu).double()
 
     xc = x.clone().requires_grad_(x_grad)
     yc = cpu(xc)
     dy = torch.randn(yc.shape, generator=dy_gen)
     yc.backward(dy)
+    cpu.zero_grad_names = _zero_grad_names(ref64, x, dy)
 
     xg = x.clone().cuda().contiguous(memory_format=CL) \
         .requires_grad_(x_grad)
@@ -58,10 +70,11 @@ def _param_grads_close(cpu, gpu):
         if pc.grad is None:
             assert pg.grad is None or pg.grad.abs().max() == 0
             continue
-        if pc.grad.abs().max() < 1e-4:
+        if name in cpu.zero_grad_names or pc.grad.abs().max() < 1e-4:
             # analytically-zero grads (conv bias under train-mode BN):
-            # CPU eager leaves ~1e-5 summation residue, the HIP path
+            # CPU eager leaves ~1e-4 summation residue, the HIP path
             # returns exact zeros — both must be ~0
+            assert pc.grad.abs().max().item() < 1e-3, f'cpu grad {name}'
             assert pg.grad.abs().max().item() < 1e-4, f'grad {name}'
             continue
         assert rel_err(pg.grad, pc.grad) < TOL, f'grad {name}'
