@@ -8,7 +8,8 @@ the 11 architecture flags from the checkpoint's sidecar pickle
 (config.py:157-158, 171-179).
 
 MI355X-specific additions live in their own group (``--engine``,
-``--bucket-cap-mb``, ``--comm-dtype``, ``--channels-last``, ``--synthetic``):
+``--bucket-cap-mb``, ``--comm-dtype``, ``--channels-last``,
+``--device-encode``, ``--synthetic``):
 they control the HIP kernel engine and the RCCL-over-xGMI gradient bucketing
 and default to the MI355X-native path.
 """
@@ -179,6 +180,12 @@ def make_parser():
                  'capture failure')
     parser.add_argument('--no-train-graph', dest='train_graph',
             action='store_false')
+    parser.add_argument('--device-encode', dest='device_encode',
+            action='store_true', default=False,
+            help='training only: loader workers ship uint8 images + padded '
+                 'boxes and the training device normalises the images and '
+                 'encodes the heatmap/offset/size/mask targets (HIP kernels '
+                 'on GPU) instead of numpy in the workers')
     parser.add_argument('--synthetic', action='store_true', default=False,
             help='use synthetic VOC2028-shaped data (no dataset on disk)')
     parser.add_argument('--synthetic-size', type=int, default=512,

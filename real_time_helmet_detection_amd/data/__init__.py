@@ -1,7 +1,7 @@
 """Data layer: VOC-XML dataset, synthetic twin, augmentors, loader factory."""
 
 from .voc import (VOC, SyntheticVOC, CLASS2INDEX, INDEX2CLASS, CLASS2COLOR,
-                  parse_voc_xml, boxes_from_voc_dict)
+                  parse_voc_xml, boxes_from_voc_dict, pack_boxes)
 from .augment import TrainAugmentor, TestAugmentor
 
 
@@ -50,4 +50,4 @@ def load_dataset(args):
 
 __all__ = ['VOC', 'SyntheticVOC', 'TrainAugmentor', 'TestAugmentor',
            'load_dataset', 'CLASS2INDEX', 'INDEX2CLASS', 'CLASS2COLOR',
-           'parse_voc_xml', 'boxes_from_voc_dict']
+           'parse_voc_xml', 'boxes_from_voc_dict', 'pack_boxes']

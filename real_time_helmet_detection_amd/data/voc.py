@@ -11,6 +11,9 @@ Capability parity with /root/reference/data.py:22-125:
   heavy CPU work runs inside DataLoader workers.
 - ``collate_fn`` -> (img, heatmap, offset, wh, mask, voc_dict_list); the voc
   dicts carry filename + original size for eval-time box rescaling.
+- ``collate_raw`` -> (img_u8, boxes, labels, voc_dict_list): the opt-in
+  ``--device-encode`` form, which leaves normalisation and target encoding
+  to the training device (ops.functional).
 
 ``SyntheticVOC`` generates VOC2028-shaped data in memory (random images,
 random plausible hat/person boxes, same voc_dict contract) for the
@@ -75,8 +78,43 @@ def boxes_from_voc_dict(voc_dict):
     return box_lst, id_lst
 
 
+def pack_boxes(boxes_lst, labels_lst, multiple=8):
+    """Per-sample box lists -> padded batch tensors for the device encoder.
+
+    Returns boxes (B,N,4) fp32 padded with zeros and labels (B,N) int32
+    padded with -1, N = the batch maximum rounded up to ``multiple`` (0 for
+    a batch without boxes). Zero-radius boxes (xmin==xmax and ymin==ymax,
+    NaN in box2hm; clip_boxes never emits them) are dropped here."""
+    kept = []
+    for boxes, labels in zip(boxes_lst, labels_lst):
+        b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+        l = np.asarray(labels, dtype=np.int32).reshape(-1)
+        ok = ~((b[:, 0] == b[:, 2]) & (b[:, 1] == b[:, 3]))
+        kept.append((b[ok], l[ok]))
+    n = max((len(b) for b, _ in kept), default=0)
+    n = -(-n // multiple) * multiple
+    boxes_t = np.zeros((len(kept), n, 4), dtype=np.float32)
+    labels_t = np.full((len(kept), n), -1, dtype=np.int32)
+    for i, (b, l) in enumerate(kept):
+        boxes_t[i, :len(b)] = b
+        labels_t[i, :len(l)] = l
+    return torch.from_numpy(boxes_t), torch.from_numpy(labels_t)
+
+
 class _CollateMixin:
     """Shared collate: batch augmentation -> heatmap encode -> tensors."""
+
+    def collate_raw(self, batch):
+        """collate_fn without the encode/normalize work: the same transform
+        call, then (img_u8 (B,H,W,3) uint8, boxes (B,N,4) fp32, labels
+        (B,N) int32, voc_dict_list) for ops.functional.normalize_images /
+        encode_targets to finish on the training device."""
+        imgs, boxes_lst, labels_lst, voc_dicts = zip(*batch)
+        imgs, boxes_lst, labels_lst = self.transform(
+            list(imgs), list(boxes_lst), list(labels_lst))
+        boxes_t, labels_t = pack_boxes(boxes_lst, labels_lst)
+        return (torch.from_numpy(np.stack(imgs)), boxes_t, labels_t,
+                list(voc_dicts))
 
     def collate_fn(self, batch):
         imgs, boxes_lst, labels_lst, voc_dicts = zip(*batch)

@@ -85,7 +85,9 @@ def distributed_worker(device, ngpus_per_node, args, env_launch=False):
         num_workers=num_workers,
         pin_memory=(dev.type == 'cuda'),
         sampler=sampler,
-        collate_fn=dataset.collate_fn,
+        collate_fn=(dataset.collate_raw
+                    if getattr(args, 'device_encode', False)
+                    else dataset.collate_fn),
         drop_last=False,
         persistent_workers=(num_workers > 0),
     )
@@ -143,6 +145,28 @@ def compute_stack_losses(outputs, loss_calculator, gt_heatmap, gt_offset,
     return total, last_heatmap
 
 
+def prepare_batch(raw, dev, args, amp_on, use_cl):
+    """--device-encode: turn a ``collate_raw`` batch (img_u8, boxes, labels)
+    into (image, gt_heatmap, gt_offset, gt_size, gt_mask) on ``dev``.
+
+    Three small uploads (uint8 pixels, padded boxes, labels), then the two
+    ops — HIP kernels on GPU, launched on the current stream ahead of (and
+    outside) the captured train-step graph; box2hm/Normalizer on CPU. The
+    image comes out bf16 under --amp (what the first conv casts to anyway)
+    and fp32 otherwise."""
+    from ..ops import functional as opsF
+    img_u8, boxes, labels = (t.to(dev, non_blocking=True) for t in raw)
+    dtype = torch.bfloat16 if (amp_on and dev.type == 'cuda') \
+        else torch.float32
+    image = opsF.normalize_images(img_u8, args.pretrained, dtype)
+    if not use_cl:
+        image = image.contiguous()
+    targets = opsF.encode_targets(
+        boxes, labels, tuple(img_u8.shape[1:3]), args.scale_factor,
+        args.num_cls, args.normalized_coord)
+    return (image, *targets)
+
+
 def _want_train_graph(args, device):
     """hipGraph capture of the full training step: GPU + HIP engine +
     no gradient accumulation (micro-steps change the per-iteration op
@@ -182,22 +206,28 @@ def train_step(dataloader, network, loss_calculator, optimizer, scheduler,
                                    amp_on=(scaler is not None))
         network._rthd_graphed = graphed
 
+    device_encode = getattr(args, 'device_encode', False)
+
     tictoc = time.time()
-    for iteration, (image, gt_heatmap, gt_offset, gt_size, gt_mask,
-                    gt_dict) in enumerate(dataloader, 1):
+    for iteration, batch in enumerate(dataloader, 1):
         time_logger['data'].update(time.time() - tictoc)
 
         step_now = (iteration % args.sub_divisions == 0) or \
             (iteration == n_batches)
 
         tictoc = time.time()
-        image = image.to(dev, non_blocking=True)
-        if use_cl:
-            image = image.to(memory_format=torch.channels_last)
-        gt_heatmap = gt_heatmap.to(dev, non_blocking=True)
-        gt_offset = gt_offset.to(dev, non_blocking=True)
-        gt_size = gt_size.to(dev, non_blocking=True)
-        gt_mask = gt_mask.to(dev, non_blocking=True)
+        if device_encode:
+            image, gt_heatmap, gt_offset, gt_size, gt_mask = prepare_batch(
+                batch[:3], dev, args, scaler is not None, use_cl)
+        else:
+            image, gt_heatmap, gt_offset, gt_size, gt_mask, gt_dict = batch
+            image = image.to(dev, non_blocking=True)
+            if use_cl:
+                image = image.to(memory_format=torch.channels_last)
+            gt_heatmap = gt_heatmap.to(dev, non_blocking=True)
+            gt_offset = gt_offset.to(dev, non_blocking=True)
+            gt_size = gt_size.to(dev, non_blocking=True)
+            gt_mask = gt_mask.to(dev, non_blocking=True)
 
         if graphed is not None and graphed.enabled:
             # whole iteration (fwd + fused loss + bwd + allreduce + Adam)

@@ -101,6 +101,13 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
                                       int64_t act,
                                       c10::optional<torch::Tensor> skip);
 torch::Tensor col_sum(torch::Tensor x);
+
+std::vector<torch::Tensor> encode_targets(torch::Tensor boxes,
+                                          torch::Tensor labels, int64_t H,
+                                          int64_t W, int64_t scale_factor,
+                                          int64_t num_cls, bool normalized);
+torch::Tensor normalize_u8(torch::Tensor img_u8, torch::Tensor table);
+int64_t encode_chunk();
 }  // namespace rthd
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -137,6 +144,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_act_fwd", &rthd::bn_act_fwd, py::arg("x"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("act"), py::arg("skip") = py::none());
   m.def("bn_act_bwd", &rthd::bn_act_bwd, py::arg("dy"), py::arg("x"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("act"), py::arg("skip") = py::none());
   m.def("col_sum", &rthd::col_sum);
+  m.def("encode_targets", &rthd::encode_targets);
+  m.def("normalize_u8", &rthd::normalize_u8);
+  m.def("encode_chunk", &rthd::encode_chunk);
 }
 
 // ---------------------------------------------------------------------------

@@ -30,6 +30,43 @@ def centernet_losses(phm, poff, psize, ghm, goff, gsize, mask,
     return hm_loss, off_loss, size_loss
 
 
+# -------------------------------------------------------- input pipeline ---
+
+def encode_targets(boxes, labels, imsize_hw, scale_factor, num_cls,
+                   normalized):
+    """Padded (B,N,4) fp32 boxes + (B,N) int32 labels (label < 0 = padding
+    row) -> [heatmap, offset, size, mask], by calling transform.box2hm per
+    sample on the float32 rows exactly as data.voc collate_fn does."""
+    import numpy as np
+    from ..transform import box2hm
+    H, W = imsize_hw
+    boxes_np = boxes.detach().cpu().numpy()
+    labels_np = labels.detach().cpu().numpy()
+    maps = [[], [], [], []]
+    for b, l in zip(boxes_np, labels_np):
+        keep = l >= 0
+        b, l = b[keep], l[keep]
+        out = box2hm(b if len(b) else None, l, (W, H),
+                     scale_factor=scale_factor, num_cls=num_cls,
+                     normalized=normalized)
+        for lst, m in zip(maps, out):
+            lst.append(m)
+    h, w = H // scale_factor, W // scale_factor
+    chans = (num_cls, 2, 2, 1)
+    return [torch.from_numpy(np.stack(lst)).to(boxes.device) if lst
+            else torch.zeros(0, c, h, w, device=boxes.device)
+            for lst, c in zip(maps, chans)]
+
+
+def normalize_images(img_u8, pretrained, dtype=torch.float32):
+    """(B,H,W,3) uint8 -> (B,3,H,W) channels_last, utils.Normalizer applied
+    to x.float()/255 (the collate_fn arithmetic), then cast to ``dtype``."""
+    from ..utils import get_normalizer
+    norm = get_normalizer(pretrained=pretrained)
+    x = norm(img_u8.permute(0, 3, 1, 2).float() / 255.0)
+    return x.to(dtype).contiguous(memory_format=torch.channels_last)
+
+
 # ---------------------------------------------------------------- conv-ish --
 
 def conv2d(x, weight, bias=None, stride=1, padding=0):

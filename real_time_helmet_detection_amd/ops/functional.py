@@ -112,6 +112,34 @@ def maxpool_same(x, kernel):
     return F.max_pool2d(x, kernel, stride=1, padding=kernel // 2)
 
 
+def encode_targets(boxes, labels, imsize_hw, scale_factor, num_cls,
+                   normalized):
+    """CenterNet training targets from a padded box batch.
+
+    boxes (B,N,4) fp32 xyxy image pixels, labels (B,N) int32 with label < 0
+    marking padding rows (N may be 0); imsize_hw = (H, W) of the input
+    images. Returns [heatmap (B,num_cls,h,w), offset (B,2,h,w),
+    size (B,2,h,w), mask (B,1,h,w)] fp32 — transform.box2hm per sample.
+    """
+    if _hip(boxes):
+        from . import hip
+        return hip.encode_targets(boxes, labels, imsize_hw, scale_factor,
+                                  num_cls, normalized)
+    from . import eager
+    return eager.encode_targets(boxes, labels, imsize_hw, scale_factor,
+                                num_cls, normalized)
+
+
+def normalize_images(img_u8, pretrained, dtype=torch.float32):
+    """(B,H,W,3) uint8 -> normalized (B,3,H,W) channels_last tensor of
+    ``dtype`` (fp32 or bf16): utils.Normalizer applied to x.float()/255."""
+    if _hip(img_u8):
+        from . import hip
+        return hip.normalize_images(img_u8, pretrained, dtype)
+    from . import eager
+    return eager.normalize_images(img_u8, pretrained, dtype)
+
+
 def upsample2x_add(x, skip=None):
     """Nearest 2x upsample, optionally fused with the hourglass skip add."""
     if _hip(x):

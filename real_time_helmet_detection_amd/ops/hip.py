@@ -661,6 +661,50 @@ def centernet_losses_logits(out, ghm, goff, gsize, mask, focal_alpha,
                                         bool(sigmoid_offsize))
 
 
+# -------------------------------------------------------- input pipeline ---
+
+def encode_targets(boxes, labels, imsize_hw, scale_factor, num_cls,
+                   normalized):
+    """Device twin of ops.eager.encode_targets (transform.box2hm per
+    sample): one gather launch, every plane written in full — no memset, no
+    atomics, capture-legal. Returns [heatmap, offset, size, mask]."""
+    H, W = imsize_hw
+    return _C().encode_targets(boxes, labels, int(H), int(W),
+                               int(scale_factor), int(num_cls),
+                               bool(normalized))
+
+
+# per-(device, scheme, dtype) 3x256 lookup tables, built by running the
+# host oracle itself on every byte value so the kernel's fp32 output is
+# bit-identical to the dataloader path by construction
+_norm_tables = {}
+
+
+def _norm_table(device, pretrained, dtype):
+    key = (device.index if device.index is not None else -1,
+           'imagenet' if pretrained == 'imagenet' else 'scratch', dtype)
+    tab = _norm_tables.get(key)
+    if tab is None:
+        from ..utils import get_normalizer
+        ramp = torch.arange(256, dtype=torch.uint8).view(1, 256, 1)
+        ramp = ramp.expand(3, 256, 1).float() / 255.0
+        tab = get_normalizer(pretrained=pretrained)(ramp).view(3, 256)
+        tab = tab.to(dtype).to(device)
+        _norm_tables[key] = tab
+    return tab
+
+
+def normalize_images(img_u8, pretrained, dtype=torch.float32):
+    """(B,H,W,3) uint8 device tensor -> normalized (B,3,H,W) channels_last
+    tensor in fp32 or bf16 (bf16 == the fp32 result cast by torch, so the
+    separate autocast cast kernel disappears)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('normalize_images: dtype must be float32 or '
+                         'bfloat16, got %r' % (dtype,))
+    return _C().normalize_u8(img_u8,
+                             _norm_table(img_u8.device, pretrained, dtype))
+
+
 # ---------------------------------------------------------------- decode ---
 
 def batched_decode(heatmap, offset, wh, scale_factor, topk, pool_size,
