@@ -18,18 +18,12 @@
 //
 // Requires Cin % 32 == 0 (every conv in the model except the 3-channel
 // stem, which has its own kernel in stem.hip).
-#include <torch/extension.h>
-#include <ATen/cuda/CUDAContext.h>
-
 #include <mutex>
 #include <unordered_map>
 
-#include "common.h"
+#include "conv_common.h"
 
 namespace rthd {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // ------------------------------ weight packing ------------------------------
 
@@ -103,23 +97,11 @@ torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16) {
 
 // ------------------------------ conv forward --------------------------------
 
-// LDS tile: 128 rows x 32 k of bf16 (64 B rows); slot swizzle:
-//   byte(row, k8) = row*64 + ((k8 ^ ((row>>2)&3))*16)
-// fp32: 128-B rows, element swizzle k' = k ^ (row & 15) within the row.
-DEV_INLINE int lds_off_bf16(int row, int k8) {
-  return row * 64 + ((k8 ^ ((row >> 2) & 3)) << 4);
-}
+// fp32 LDS tile: 128-B rows, element swizzle k' = k ^ (row & 15) within
+// the row (the bf16 tile uses lds_off_row64 from conv_common.h).
 DEV_INLINE int lds_off_f32(int row, int k) {
   return row * 128 + ((k ^ (row & 15)) << 2);
 }
-
-struct ConvGeo {
-  int B, H, W, Cin, Ho, Wo, Cout;
-  int KH, KW, stride, pad;
-  int Cinp;   // padded Cin (mult of 32)
-  int Coutp;  // padded Cout (mult of 128)
-  int M;      // B*Ho*Wo
-};
 
 // act codes from common.h; epilogue: y = act(acc*scale[c] + shift[c] (+skip))
 //
@@ -131,13 +113,8 @@ struct ConvGeo {
 // pixels point their source at a 16-B zero page (glds cannot select-zero).
 // The per-lane SOURCE k8 is pre-swizzled so the lane-linear LDS image equals
 // the XOR-swizzled layout the fragment reads expect (guide rule 21).
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-
-// STATS: also emit per-(mblk,wave-row) column partial sums/sumsq of the
-// stored values into sp1/sp2[2*gridDim.x][Cout] — the training-BN stats
-// then come from the fixed-order partial reduce instead of a separate
-// full pass over y (cross-lane combine via xor-shuffles: deterministic).
+// STATS: conv_epilogue's column partials go to sp1/sp2[2*gridDim.x][Cout],
+// one row per (mblk, wave-row).
 template <bool HAS_SKIP, bool STATS = false>
 __global__ __launch_bounds__(256)
 void conv_fwd_bf16_kernel(const bf16* __restrict__ x,
@@ -180,13 +157,8 @@ void conv_fwd_bf16_kernel(const bf16* __restrict__ x,
   int am[2], ab[2], ay[2], ax[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int m = mblk * 128 + st_row + 64 * h;
-    am[h] = m;
-    const int mm = m < g.M ? m : 0;
-    ab[h] = mm / (g.Ho * g.Wo);
-    const int r = mm % (g.Ho * g.Wo);
-    ay[h] = r / g.Wo;
-    ax[h] = r % g.Wo;
+    am[h] = mblk * 128 + st_row + 64 * h;
+    pixel_decompose(am[h], g, &ab[h], &ay[h], &ax[h]);
   }
 
   const int kc = g.Cinp / 32;
@@ -265,9 +237,9 @@ void conv_fwd_bf16_kernel(const bf16* __restrict__ x,
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       afrag[i] = *reinterpret_cast<const bf16x8*>(
-          A + lds_off_bf16(arow_base + 16 * i, k8));
+          A + lds_off_row64(arow_base + 16 * i, k8));
       bfrag[i] = *reinterpret_cast<const bf16x8*>(
-          B + lds_off_bf16(brow_base + 16 * i, k8));
+          B + lds_off_row64(brow_base + 16 * i, k8));
     }
     // MFMA-phase issue priority (measured +6% on the wgrad kernel: the
     // co-resident waves still issuing staging yield slots to the MFMAs)
@@ -292,60 +264,11 @@ void conv_fwd_bf16_kernel(const bf16* __restrict__ x,
     __builtin_amdgcn_s_barrier();
   }
 
-  // ---- epilogue ----
-  // preload the 4 per-lane scale/shift pairs ONCE (the per-store scalar
-  // loads serialized the epilogue: 65 dependent vmcnt(0) waits in the .s)
-  const int col0 = nblk * 128 + wc * 64 + (lane & 15);
-  float esc[4], esh[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int c = col0 + ni * 16;
-    esc[ni] = c < g.Cout ? scale[c] : 0.f;
-    esh[ni] = c < g.Cout ? shift[c] : 0.f;
-  }
-  const int row_in_frag = (lane >> 4) * 4;
-  float s1[4] = {}, s2[4] = {};
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = mblk * 128 + wr * 64 + mi * 16 + row_in_frag + r;
-      if (m >= g.M) continue;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int c = col0 + ni * 16;
-        if (c >= g.Cout) continue;
-        float v = acc[mi][ni][r];
-        v = v * esc[ni] + esh[ni];
-        if (HAS_SKIP) v += ldf(&skip[(int64_t)m * g.Cout + c]);
-        v = apply_act(v, act);
-        stf(&y[(int64_t)m * g.Cout + c], v);
-        if (STATS) {
-          s1[ni] += v;
-          s2[ni] += v * v;
-        }
-      }
-    }
-  }
-  if (STATS) {
-    // lanes {l, l^16, l^32, l^48} hold the same columns over disjoint
-    // rows: fixed-order xor-shuffle combine, lanes 0..15 write the
-    // wave's partial row (chunk = mblk*2 + wr)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      float a = s1[ni], b = s2[ni];
-      a += __shfl_xor(a, 16, 64);
-      a += __shfl_xor(a, 32, 64);
-      b += __shfl_xor(b, 16, 64);
-      b += __shfl_xor(b, 32, 64);
-      const int c = col0 + ni * 16;
-      if ((lane >> 4) == 0 && c < g.Cout) {
-        const int64_t chunk = (int64_t)mblk * 2 + wr;
-        sp1[chunk * g.Cout + c] = a;
-        sp2[chunk * g.Cout + c] = b;
-      }
-    }
-  }
+  // stats partial row: chunk = mblk*2 + wr
+  conv_epilogue<4, 4, HAS_SKIP, STATS>(
+      acc, mblk * 128 + wr * 64, nblk * 128 + wc * 64 + (lane & 15), lane,
+      g.M, g.Cout, scale, shift, skip, y, act, sp1, sp2,
+      (int64_t)mblk * 2 + wr);
 }
 
 // fp32-exact variant: v_mfma_f32_16x16x4_f32, one A/B float per lane
@@ -371,22 +294,15 @@ void conv_fwd_f32_kernel(const float* __restrict__ x,
 
   f32x4 acc[4][4] = {};
 
-  const int st_row = tid >> 2;   // 2 rows per thread per tile
-  const int st_k4 = tid & 3;     // 4 floats (16 B) x ... k chunk of 8? no:
-  // A tile rows are 32 floats (128 B): 8 chunks of 16 B -> use 2 passes of
-  // 4-chunk? Simplest: each thread stages 2 rows x 8 floats:
+  // A tile rows are 32 floats (128 B); each thread stages 2 rows x 8 floats
+  const int st_row = tid >> 2;
   const int st_k8 = (tid & 3) * 8;
 
   int am[2], ab[2], ayy[2], axx[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int m = mblk * 128 + st_row + 64 * h;
-    am[h] = m;
-    const int mm = m < g.M ? m : 0;
-    ab[h] = mm / (g.Ho * g.Wo);
-    const int r = mm % (g.Ho * g.Wo);
-    ayy[h] = r / g.Wo;
-    axx[h] = r % g.Wo;
+    am[h] = mblk * 128 + st_row + 64 * h;
+    pixel_decompose(am[h], g, &ab[h], &ayy[h], &axx[h]);
   }
 
   const int nsteps = g.KH * g.KW * (g.Cinp / 32);
@@ -464,33 +380,9 @@ void conv_fwd_f32_kernel(const float* __restrict__ x,
     __syncthreads();
   }
 
-  const int col0 = nblk * 128 + wc * 64 + (lane & 15);
-  float esc[4], esh[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int c = col0 + ni * 16;
-    esc[ni] = c < g.Cout ? scale[c] : 0.f;
-    esh[ni] = c < g.Cout ? shift[c] : 0.f;
-  }
-  const int row_in_frag = (lane >> 4) * 4;
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = mblk * 128 + wr * 64 + mi * 16 + row_in_frag + r;
-      if (m >= g.M) continue;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int c = col0 + ni * 16;
-        if (c >= g.Cout) continue;
-        float v = acc[mi][ni][r];
-        v = v * esc[ni] + esh[ni];
-        if (HAS_SKIP) v += skip[(int64_t)m * g.Cout + c];
-        v = apply_act(v, act);
-        y[(int64_t)m * g.Cout + c] = v;
-      }
-    }
-  }
+  conv_epilogue<4, 4, HAS_SKIP, false>(
+      acc, mblk * 128 + wr * 64, nblk * 128 + wc * 64 + (lane & 15), lane,
+      g.M, g.Cout, scale, shift, skip, y, act, nullptr, nullptr, 0);
 }
 
 // ---------------------------- autotune cache --------------------------------
@@ -499,18 +391,6 @@ void conv_fwd_f32_kernel(const float* __restrict__ x,
 // (+split-K) variants on the current stream and caches the winner; under
 // stream capture (hipGraph) or RTHD_NO_AUTOTUNE an unseen shape takes the
 // fill-based heuristic instead (no timing APIs are capture-legal).
-
-torch::Tensor conv_fwd_small(torch::Tensor x, torch::Tensor wpk,
-                             torch::Tensor scale, torch::Tensor shift,
-                             c10::optional<torch::Tensor> skip,
-                             int64_t KH, int64_t KW, int64_t stride,
-                             int64_t pad, int64_t Cout, int64_t act,
-                             int64_t splitk);
-torch::Tensor conv_fwd_k64(torch::Tensor x, torch::Tensor wpk,
-                           torch::Tensor scale, torch::Tensor shift,
-                           c10::optional<torch::Tensor> skip,
-                           int64_t KH, int64_t KW, int64_t stride,
-                           int64_t pad, int64_t Cout, int64_t act);
 
 // per-device cached 16-B zero page for the glds out-of-range source (a
 // fresh torch::zeros({8}) per conv call was ~85 FillFunctor launches per
@@ -530,6 +410,9 @@ const bf16* zero_page_bf16(const torch::Tensor& like) {
 
 namespace {
 
+// variants: 0 = the 128x128/K32 kernel of this file, 1 = 64x64 split-K
+// (small spatial / Cout<=64 fill), 2 = 128x128/K64 double-buffer (fewer
+// barriers+glds issues per channel)
 struct ConvChoice { int small; int splitk; };
 
 std::mutex g_conv_tune_mu;
@@ -553,8 +436,8 @@ bool stream_capturing(hipStream_t s) {
   return st != hipStreamCaptureStatusNone;
 }
 
-// median-of-3 time of fn() in usec on stream s (fn must enqueue its work
-// on s); synchronizes the stream
+// min-of-3 time of fn() in usec on stream s after one warm run (fn must
+// enqueue its work on s); synchronizes the stream
 template <typename F>
 float time_usec(F&& fn, hipStream_t s) {
   hipEvent_t e0, e1;
@@ -576,6 +459,76 @@ float time_usec(F&& fn, hipStream_t s) {
   return best;
 }
 
+// 128x128/K32 bf16 kernel on prepared operands; p1/p2 (both or neither,
+// no skip) select the fused-stats epilogue
+void launch_big(const ConvGeo& g, const ConvOperands& o, int act,
+                float* p1, float* p2) {
+  TORCH_CHECK(!(p1 && o.skip.defined()), "conv big: stats with skip");
+  dim3 grid(cdiv(g.M, 128), g.Coutp / 128);
+  auto s = at::cuda::getCurrentCUDAStream();
+#define RTHD_BIG_LAUNCH(SKIP_, STATS_)                                     \
+  hipLaunchKernelGGL((conv_fwd_bf16_kernel<SKIP_, STATS_>), grid,          \
+      dim3(256), 3 * 16384, s, conv_ptr<const bf16>(o.x),                  \
+      conv_ptr<const bf16>(o.wpk), o.scale.data_ptr<float>(),              \
+      o.shift.data_ptr<float>(), conv_ptr<const bf16>(o.skip),             \
+      zero_page_bf16(o.x), conv_ptr<bf16>(o.y), g, act, p1, p2)
+  if (p1)                    RTHD_BIG_LAUNCH(false, true);
+  else if (o.skip.defined()) RTHD_BIG_LAUNCH(true, false);
+  else                       RTHD_BIG_LAUNCH(false, false);
+#undef RTHD_BIG_LAUNCH
+  HIP_CHECK_LAST();
+}
+
+// per-shape bf16 variant: the cached choice, else (first sight of the
+// shape) the heuristic or a measurement, cached once decided
+ConvChoice choose_conv_variant(const ConvGeo& g, const ConvOperands& o,
+                               int act) {
+  const uint64_t key = conv_key(g);
+  {
+    std::lock_guard<std::mutex> lk(g_conv_tune_mu);
+    auto it = g_conv_tune.find(key);
+    if (it != g_conv_tune.end()) return it->second;
+  }
+  // split-K candidates only where fill is the problem
+  const int big_blocks = (int)cdiv(g.M, 128) * (g.Coutp / 128);
+  const int nsteps = g.KH * g.KW * (g.Cinp / 32);
+  const int base64 = (int)cdiv(g.M, 64) * (int)cdiv(g.Cout, 64);
+  std::vector<int> cands;
+  if (big_blocks < 512 || g.Cout <= 64) {
+    for (int sk : {1, 2, 4, 8, 16}) {
+      if (sk > 1 && (nsteps + sk - 1) / sk < 2) break;
+      if ((int64_t)base64 * sk > 16384) break;
+      cands.push_back(sk);
+    }
+  }
+  ConvChoice ch{0, 1};
+  auto s = at::cuda::getCurrentCUDAStream();
+  if (stream_capturing(s) || getenv("RTHD_NO_AUTOTUNE")) {
+    if (big_blocks >= 512 && g.Cout > 64) {
+      ch = {0, 1};
+    } else if (!cands.empty()) {
+      ch = {1, cands.back()};
+      for (int sk : cands) {
+        if (base64 * sk >= 768) { ch = {1, sk}; break; }
+      }
+    }
+  } else {
+    float best = time_usec(
+        [&] { launch_big(g, o, act, nullptr, nullptr); }, s.stream());
+    const float tk = time_usec(
+        [&] { launch_k64(g, o, act, nullptr, nullptr); }, s.stream());
+    if (tk < best) { best = tk; ch = {2, 1}; }
+    for (int sk : cands) {
+      const float t = time_usec(
+          [&] { launch_small(g, o, act, sk); }, s.stream());
+      if (t < best) { best = t; ch = {1, sk}; }
+    }
+  }
+  std::lock_guard<std::mutex> lk(g_conv_tune_mu);
+  g_conv_tune[key] = ch;
+  return ch;
+}
+
 }  // namespace
 
 // host wrapper; x NCHW-logical channels_last; wpk from pack_weights.
@@ -584,151 +537,37 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wpk,
                        c10::optional<torch::Tensor> skip,
                        int64_t KH, int64_t KW, int64_t stride, int64_t pad,
                        int64_t Cout, int64_t act) {
-  auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
-  ConvGeo g;
-  g.B = xc.size(0);
-  g.Cin = xc.size(1);
-  g.H = xc.size(2);
-  g.W = xc.size(3);
-  g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-  g.Ho = (g.H + 2 * g.pad - (int)KH) / (int)stride + 1;
-  g.Wo = (g.W + 2 * g.pad - (int)KW) / (int)stride + 1;
-  g.Cout = Cout;
-  g.Cinp = (int)cdiv(g.Cin, 64) * 64;  // pack_weights 64-pad
-  g.Coutp = (int)cdiv(Cout, 128) * 128;
-  g.M = g.B * g.Ho * g.Wo;
-  TORCH_CHECK(g.Cin >= 1, "conv_fwd: bad Cin");
-  TORCH_CHECK(wpk.size(0) == KH * KW && wpk.size(1) == g.Coutp &&
-              wpk.size(2) == g.Cinp, "conv_fwd: packed weight shape");
-
   const bool bf16_mode = wpk.scalar_type() == at::kBFloat16;
-  auto out_dtype = bf16_mode ? at::kBFloat16 : at::kFloat;
-  auto y = torch::empty({g.B, (int64_t)g.Cout, g.Ho, g.Wo},
-                        xc.options().dtype(out_dtype)
-                        .memory_format(at::MemoryFormat::ChannelsLast));
-  auto sc = scale.to(at::kFloat).contiguous();
-  auto sh = shift.to(at::kFloat).contiguous();
+  TORCH_CHECK(bf16_mode || x.scalar_type() == at::kFloat,
+              "f32 conv needs f32 input");
+  const ConvGeo g = make_conv_geo("conv_fwd", x, wpk, KH, KW, stride, pad,
+                                  Cout, 64);
+  const auto dtype = bf16_mode ? at::kBFloat16 : at::kFloat;
+  auto o = prep_conv_operands(g, x, wpk, scale, shift, skip, dtype, dtype);
 
-  const bool has_skip = skip.has_value();
-  torch::Tensor sk;
-  if (has_skip)
-    sk = skip->to(out_dtype).contiguous(at::MemoryFormat::ChannelsLast);
+  if (bf16_mode) {
+    const ConvChoice ch = choose_conv_variant(g, o, (int)act);
+    if (ch.small == 1)      launch_small(g, o, (int)act, ch.splitk);
+    else if (ch.small == 2) launch_k64(g, o, (int)act, nullptr, nullptr);
+    else                    launch_big(g, o, (int)act, nullptr, nullptr);
+    return o.y;
+  }
 
   dim3 grid(cdiv(g.M, 128), g.Coutp / 128);
   auto s = at::cuda::getCurrentCUDAStream();
-
-  if (bf16_mode) {
-    const size_t lds = 3 * 16384;
-    if (xc.scalar_type() != at::kBFloat16) xc = xc.to(at::kBFloat16);
-    TORCH_CHECK(g.Cin % 8 == 0,
-                "bf16 conv requires Cin % 8 == 0 (glds staging); "
-                "Cin=", g.Cin, " runs the f32 path");
-
-    // -------- per-shape variant selection (autotune cache) --------
-    // variants: 0 = this 128x128/K32 kernel, 1 = 64x64 split-K (small
-    // spatial / Cout<=64 fill), 2 = 128x128/K64 double-buffer (fewer
-    // barriers+glds issues per channel). First eligible call measures.
-    const int big_blocks = (int)cdiv(g.M, 128) * (g.Coutp / 128);
-    {
-      ConvChoice ch{0, 1};
-      bool have = false;
-      const uint64_t key = conv_key(g);
-      {
-        std::lock_guard<std::mutex> lk(g_conv_tune_mu);
-        auto it = g_conv_tune.find(key);
-        if (it != g_conv_tune.end()) { ch = it->second; have = true; }
-      }
-      if (!have) {
-        // split-K candidates only where fill is the problem
-        const int nsteps = (int)(KH * KW) * (g.Cinp / 32);
-        const int base64 = (int)cdiv(g.M, 64) * (int)cdiv(g.Cout, 64);
-        std::vector<int> cands;
-        if (big_blocks < 512 || g.Cout <= 64) {
-          for (int sk : {1, 2, 4, 8, 16}) {
-            if (sk > 1 && (nsteps + sk - 1) / sk < 2) break;
-            if ((int64_t)base64 * sk > 16384) break;
-            cands.push_back(sk);
-          }
-        }
-        if (stream_capturing(s) || getenv("RTHD_NO_AUTOTUNE")) {
-          if (big_blocks >= 512 && g.Cout > 64) {
-            ch = {0, 1};
-          } else if (!cands.empty()) {
-            ch = {1, cands.back()};
-            for (int sk : cands) {
-              if (base64 * sk >= 768) { ch = {1, sk}; break; }
-            }
-          }
-        } else {
-          float best;
-          {  // time the big kernel: temporarily pin choice to big
-            std::lock_guard<std::mutex> lk(g_conv_tune_mu);
-            g_conv_tune[key] = ConvChoice{0, 1};
-          }
-          best = time_usec([&] {
-            (void)conv_fwd(xc, wpk, scale, shift, skip, KH, KW, stride,
-                           pad, Cout, act);
-          }, s.stream());
-          ch = {0, 1};
-          float tk = time_usec([&] {
-            (void)conv_fwd_k64(xc, wpk, scale, shift, skip, KH, KW,
-                               stride, pad, Cout, act);
-          }, s.stream());
-          if (tk < best) { best = tk; ch = {2, 1}; }
-          for (int sk : cands) {
-            float t = time_usec([&] {
-              (void)conv_fwd_small(xc, wpk, scale, shift, skip, KH, KW,
-                                   stride, pad, Cout, act, sk);
-            }, s.stream());
-            if (t < best) { best = t; ch = {1, sk}; }
-          }
-        }
-        std::lock_guard<std::mutex> lk(g_conv_tune_mu);
-        g_conv_tune[key] = ch;
-      }
-      if (ch.small == 1)
-        return conv_fwd_small(xc, wpk, scale, shift, skip, KH, KW, stride,
-                              pad, Cout, act, ch.splitk);
-      if (ch.small == 2)
-        return conv_fwd_k64(xc, wpk, scale, shift, skip, KH, KW, stride,
-                            pad, Cout, act);
-    }
-
-    auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
-    auto* pw = reinterpret_cast<const bf16*>(wpk.data_ptr());
-    auto* py = reinterpret_cast<bf16*>(y.data_ptr());
-    const bf16* pz = zero_page_bf16(xc);
-    const bf16* ps =
-        has_skip ? reinterpret_cast<const bf16*>(sk.data_ptr()) : nullptr;
-    if (has_skip)
-      hipLaunchKernelGGL((conv_fwd_bf16_kernel<true>), grid,
-          dim3(256), lds, s, px, pw, sc.data_ptr<float>(),
-          sh.data_ptr<float>(), ps, pz, py, g, (int)act);
-    else
-      hipLaunchKernelGGL((conv_fwd_bf16_kernel<false>), grid,
-          dim3(256), lds, s, px, pw, sc.data_ptr<float>(),
-          sh.data_ptr<float>(), ps, pz, py, g, (int)act);
-  } else {
-    const size_t lds = 32768;
-    TORCH_CHECK(xc.scalar_type() == at::kFloat, "f32 conv needs f32 input");
-    const float* ps = has_skip ? sk.data_ptr<float>() : nullptr;
-    if (has_skip)
-      hipLaunchKernelGGL((conv_fwd_f32_kernel<true>), grid, dim3(256), lds,
-          s, xc.data_ptr<float>(), wpk.data_ptr<float>(),
-          sc.data_ptr<float>(), sh.data_ptr<float>(), ps,
-          y.data_ptr<float>(), g, (int)act);
-    else
-      hipLaunchKernelGGL((conv_fwd_f32_kernel<false>), grid, dim3(256), lds,
-          s, xc.data_ptr<float>(), wpk.data_ptr<float>(),
-          sc.data_ptr<float>(), sh.data_ptr<float>(), ps,
-          y.data_ptr<float>(), g, (int)act);
-  }
+  if (o.skip.defined())
+    hipLaunchKernelGGL((conv_fwd_f32_kernel<true>), grid, dim3(256), 32768,
+        s, o.x.data_ptr<float>(), wpk.data_ptr<float>(),
+        o.scale.data_ptr<float>(), o.shift.data_ptr<float>(),
+        o.skip.data_ptr<float>(), o.y.data_ptr<float>(), g, (int)act);
+  else
+    hipLaunchKernelGGL((conv_fwd_f32_kernel<false>), grid, dim3(256), 32768,
+        s, o.x.data_ptr<float>(), wpk.data_ptr<float>(),
+        o.scale.data_ptr<float>(), o.shift.data_ptr<float>(),
+        (const float*)nullptr, o.y.data_ptr<float>(), g, (int)act);
   HIP_CHECK_LAST();
-  return y;
+  return o.y;
 }
-
-
-
 
 // ---------------------- training-BN fused-stats forward ---------------------
 // y = act(conv*scale + shift) PLUS the per-column sum/sumsq partials the
@@ -738,128 +577,31 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wpk,
 // (deterministic). When the autotuned variant for this shape is the
 // split-K small kernel (no stats epilogue), returns {y} and the caller
 // falls back to the standalone reduction.
-
-torch::Tensor conv_fwd_k64_stats(torch::Tensor x, torch::Tensor wpk,
-                                 torch::Tensor scale, torch::Tensor shift,
-                                 int64_t KH, int64_t KW, int64_t stride,
-                                 int64_t pad, int64_t Cout, int64_t act,
-                                 torch::Tensor p1, torch::Tensor p2);
-
 std::vector<torch::Tensor> conv_fwd_stats(
     torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
     torch::Tensor shift, int64_t KH, int64_t KW, int64_t stride,
     int64_t pad, int64_t Cout, int64_t act) {
-  auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   TORCH_CHECK(wpk.scalar_type() == at::kBFloat16,
               "conv_fwd_stats: bf16 only (f32 path uses bn_stats)");
-  if (xc.scalar_type() != at::kBFloat16) xc = xc.to(at::kBFloat16);
-  ConvGeo g;
-  g.B = xc.size(0);
-  g.Cin = xc.size(1);
-  g.H = xc.size(2);
-  g.W = xc.size(3);
-  g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-  g.Ho = (g.H + 2 * g.pad - (int)KH) / (int)stride + 1;
-  g.Wo = (g.W + 2 * g.pad - (int)KW) / (int)stride + 1;
-  g.Cout = Cout;
-  g.Cinp = (int)cdiv(g.Cin, 64) * 64;
-  g.Coutp = (int)cdiv(Cout, 128) * 128;
-  g.M = g.B * g.Ho * g.Wo;
-  TORCH_CHECK(g.Cin % 8 == 0, "conv_fwd_stats: Cin % 8 required");
-
-  // consult (and if needed, prime) the variant cache
-  const uint64_t key = conv_key(g);
-  ConvChoice ch{0, 1};
-  bool have = false;
-  {
-    std::lock_guard<std::mutex> lk(g_conv_tune_mu);
-    auto it = g_conv_tune.find(key);
-    if (it != g_conv_tune.end()) { ch = it->second; have = true; }
-  }
-  if (!have) {
-    (void)conv_fwd(xc, wpk, scale, shift, c10::nullopt, KH, KW, stride,
-                   pad, Cout, act);
-    std::lock_guard<std::mutex> lk(g_conv_tune_mu);
-    auto it = g_conv_tune.find(key);
-    if (it != g_conv_tune.end()) ch = it->second;
-  }
+  const ConvGeo g = make_conv_geo("conv_fwd_stats", x, wpk, KH, KW, stride,
+                                  pad, Cout, 64);
+  auto o = prep_conv_operands(g, x, wpk, scale, shift, c10::nullopt,
+                              at::kBFloat16, at::kBFloat16);
+  const ConvChoice ch = choose_conv_variant(g, o, (int)act);
   if (ch.small == 1) {
     // split-K variant has no stats epilogue — caller runs bn_stats
-    auto y = conv_fwd(xc, wpk, scale, shift, c10::nullopt, KH, KW,
-                      stride, pad, Cout, act);
-    return {y};
+    launch_small(g, o, (int)act, ch.splitk);
+    return {o.y};
   }
-
-  const int mblks = (int)cdiv(g.M, 128);
-  auto p1 = torch::empty({(int64_t)2 * mblks, (int64_t)Cout},
-                         xc.options().dtype(at::kFloat));
+  auto p1 = torch::empty({2 * cdiv(g.M, 128), Cout},
+                         o.x.options().dtype(at::kFloat));
   auto p2 = torch::empty_like(p1);
-  auto sc = scale.to(at::kFloat).contiguous();
-  auto sh = shift.to(at::kFloat).contiguous();
-
-  if (ch.small == 2) {
-    auto y = conv_fwd_k64_stats(xc, wpk, sc, sh, KH, KW, stride, pad,
-                                Cout, act, p1, p2);
-    return {y, p1, p2};
-  }
-
-  auto y = torch::empty({g.B, (int64_t)g.Cout, g.Ho, g.Wo},
-                        xc.options().memory_format(
-                            at::MemoryFormat::ChannelsLast));
-  dim3 grid(mblks, g.Coutp / 128);
-  auto s = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL((conv_fwd_bf16_kernel<false, true>), grid, dim3(256),
-      3 * 16384, s, reinterpret_cast<const bf16*>(xc.data_ptr()),
-      reinterpret_cast<const bf16*>(wpk.data_ptr()), sc.data_ptr<float>(),
-      sh.data_ptr<float>(), nullptr, zero_page_bf16(xc),
-      reinterpret_cast<bf16*>(y.data_ptr()), g, (int)act,
-      p1.data_ptr<float>(), p2.data_ptr<float>());
-  HIP_CHECK_LAST();
-  return {y, p1, p2};
-}
-
-// pack pre-scaled fp32 weights to fp8 e4m3 [T][Coutp][Cinp]
-__global__ void pack_weights_fp8_kernel(const float* __restrict__ w,
-                                        unsigned char* __restrict__ pk,
-                                        int Cout, int Cin, int KH, int KW,
-                                        int64_t s0, int64_t s1, int64_t s2,
-                                        int64_t s3,
-                                        int Rp, int Kp) {
-  const int T_ = KH * KW;
-  const int64_t n = (int64_t)T_ * Rp * Kp;
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const int t = i / ((int64_t)Rp * Kp);
-    const int row = (i / Kp) % Rp;
-    const int k = i % Kp;
-    float v = 0.f;
-    if (row < Cout && k < Cin)
-      v = w[row * s0 + k * s1 + (t / KW) * s2 + (t % KW) * s3];
-    const unsigned p = __builtin_amdgcn_cvt_pk_fp8_f32(v, 0.f, 0, false);
-    pk[i] = (unsigned char)(p & 0xff);
-  }
-}
-
-torch::Tensor pack_weights_fp8(torch::Tensor w) {
-  auto wc = w.to(at::kFloat);
-  const int Cout = wc.size(0), Cin = wc.size(1);
-  const int KH = wc.size(2), KW = wc.size(3);
-  const int T_ = KH * KW;
-  const int Rp = (int)cdiv(Cout, 128) * 128;
-  // K pads to 128: one mfma_scale_f32_16x16x128 K-block per tap chunk
-  const int Kp = (int)cdiv(Cin, 128) * 128;
-  auto pk = torch::empty({T_, Rp, Kp},
-                         wc.options().dtype(at::kFloat8_e4m3fn));
-  const int64_t n = (int64_t)T_ * Rp * Kp;
-  auto s = at::cuda::getCurrentCUDAStream();
-  const auto ws = wc.strides();
-  hipLaunchKernelGGL(pack_weights_fp8_kernel, dim3(ew_grid(n, 256)),
-      dim3(256), 0, s, wc.data_ptr<float>(),
-      reinterpret_cast<unsigned char*>(pk.data_ptr()), Cout, Cin, KH, KW,
-      ws[0], ws[1], ws[2], ws[3], Rp, Kp);
-  HIP_CHECK_LAST();
-  return pk;
+  if (ch.small == 2)
+    launch_k64(g, o, (int)act, p1.data_ptr<float>(), p2.data_ptr<float>());
+  else
+    launch_big(g, o, (int)act, p1.data_ptr<float>(), p2.data_ptr<float>());
+  return {o.y, p1, p2};
 }
 
 }  // namespace rthd
+

@@ -14,33 +14,9 @@
 // lane-linear glds image equals the XOR-swizzled layout the fragment
 // ds_read_b128s expect. bf16 only — the f32-exact path keeps the 128x128
 // kernel (fill is not its bottleneck in the fp32 engine).
-#include <torch/extension.h>
-#include <ATen/cuda/CUDAContext.h>
-#include "common.h"
+#include "conv_common.h"
 
 namespace rthd {
-
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-const bf16* zero_page_bf16(const torch::Tensor& like);  // conv.hip
-
-DEV_INLINE int lds_off_bf16_s(int row, int k8) {
-  return row * 64 + ((k8 ^ ((row >> 2) & 3)) << 4);
-}
-
-struct ConvGeoS {
-  int B, H, W, Cin, Ho, Wo, Cout;
-  int KH, KW, stride, pad;
-  int Cinp;
-  int Coutp;   // pack_weights pads rows to 128; N blocks are 64 here
-  int M;
-  int nsteps;  // taps * Cinp/32
-  int chunk;   // K steps per z-block (split-K)
-};
-
-typedef __attribute__((address_space(3))) void lds_void_s;
-typedef __attribute__((address_space(1))) const void glb_void_s;
 
 // SPLIT=true: write fp32 partials to part[z][M][Coutp64] (no epilogue).
 // SPLIT=false: fused scale/shift/act(+skip) epilogue straight to y.
@@ -54,7 +30,8 @@ void conv_fwd_bf16_64_kernel(const bf16* __restrict__ x,
                              const bf16* __restrict__ zpage,
                              bf16* __restrict__ y,
                              float* __restrict__ part, int Coutp64,
-                             ConvGeoS g, int act) {
+                             ConvGeo g, int ksteps, int kchunk, int act) {
+  // ksteps = taps * Cinp/32 in all; kchunk = K steps per z-block (split-K)
   const int mblk = blockIdx.x;
   const int nblk = blockIdx.y;
   const int z = blockIdx.z;
@@ -73,22 +50,15 @@ void conv_fwd_bf16_64_kernel(const bf16* __restrict__ x,
   const int k8s = st_k8 ^ ((st_row >> 2) & 3);
   const int wbase = wid * 1024;
 
-  int am, ab, ay, ax;
-  {
-    const int m = mblk * 64 + st_row;
-    am = m;
-    const int mm = m < g.M ? m : 0;
-    ab = mm / (g.Ho * g.Wo);
-    const int r = mm % (g.Ho * g.Wo);
-    ay = r / g.Wo;
-    ax = r % g.Wo;
-  }
+  const int am = mblk * 64 + st_row;
+  int ab, ay, ax;
+  pixel_decompose(am, g, &ab, &ay, &ax);
 
   const int kc = g.Cinp / 32;
   const int taps = g.KH * g.KW;
-  const int s0 = z * g.chunk;
-  int s1 = s0 + g.chunk;
-  if (s1 > g.nsteps) s1 = g.nsteps;
+  const int s0 = z * kchunk;
+  int s1 = s0 + kchunk;
+  if (s1 > ksteps) s1 = ksteps;
   const int nsteps = s1 - s0;
   if (nsteps <= 0) return;  // ragged last z-block
 
@@ -115,10 +85,10 @@ void conv_fwd_bf16_64_kernel(const bf16* __restrict__ x,
     char* base = lds + (is_step % 3) * 8192;
     const int cb = is_kb * 32;
     const bf16* a0 = (avalid && cb + k8s * 8 < g.Cin) ? aptr + cb : zpage;
-    __builtin_amdgcn_global_load_lds((glb_void_s*)a0,
-        (lds_void_s*)(base + wbase), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((glb_void_s*)(bptr + cb),
-        (lds_void_s*)(base + 4096 + wbase), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_void*)a0,
+        (lds_void*)(base + wbase), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_void*)(bptr + cb),
+        (lds_void*)(base + 4096 + wbase), 16, 0, 0);
     ++is_step;
     if (++is_kb == kc) {
       is_kb = 0;
@@ -147,9 +117,9 @@ void conv_fwd_bf16_64_kernel(const bf16* __restrict__ x,
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       afrag[i] = *reinterpret_cast<const bf16x8*>(
-          A + lds_off_bf16_s(arow_base + 16 * i, k8));
+          A + lds_off_row64(arow_base + 16 * i, k8));
       bfrag[i] = *reinterpret_cast<const bf16x8*>(
-          B + lds_off_bf16_s(brow_base + 16 * i, k8));
+          B + lds_off_row64(brow_base + 16 * i, k8));
     }
     asm volatile("s_setprio 1");
 #pragma unroll
@@ -187,31 +157,9 @@ void conv_fwd_bf16_64_kernel(const bf16* __restrict__ x,
       }
     }
   } else {
-    float esc[2], esh[2];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      const int c = col0 + ni * 16;
-      esc[ni] = c < g.Cout ? scale[c] : 0.f;
-      esh[ni] = c < g.Cout ? shift[c] : 0.f;
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = mblk * 64 + wr * 32 + mi * 16 + row_in_frag + r;
-        if (m >= g.M) continue;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const int c = col0 + ni * 16;
-          if (c >= g.Cout) continue;
-          float v = acc[mi][ni][r];
-          v = v * esc[ni] + esh[ni];
-          if (HAS_SKIP) v += ldf(&skip[(int64_t)m * g.Cout + c]);
-          v = apply_act(v, act);
-          stf(&y[(int64_t)m * g.Cout + c], v);
-        }
-      }
-    }
+    conv_epilogue<2, 2, HAS_SKIP, false>(
+        acc, mblk * 64 + wr * 32, col0, lane, g.M, g.Cout, scale, shift,
+        skip, y, act, nullptr, nullptr, 0);
   }
 }
 
@@ -240,94 +188,73 @@ __global__ void conv_splitk_reduce_kernel(const float* __restrict__ part,
   }
 }
 
-// host entry: BM=BN=64 (+split-K) path; geometry mirrors conv_fwd
+// BM=BN=64 (+split-K) path on prepared bf16 operands
+void launch_small(const ConvGeo& g, const ConvOperands& o, int act,
+                  int splitk) {
+  const int ksteps = g.KH * g.KW * (g.Cinp / 32);
+  int SK = splitk;
+  if (SK < 1) SK = 1;
+  if (SK > ksteps) SK = ksteps;
+  const int kchunk = (int)cdiv(ksteps, SK);
+  SK = (int)cdiv(ksteps, kchunk);  // drop empty z-blocks
+
+  const bool has_skip = o.skip.defined();
+  const int nblkN = (int)cdiv(g.Cout, 64);
+  const int Coutp64 = nblkN * 64;
+  dim3 grid(cdiv(g.M, 64), nblkN, SK);
+  auto s = at::cuda::getCurrentCUDAStream();
+  const size_t lds = 3 * 8192;
+
+  auto* px = conv_ptr<const bf16>(o.x);
+  auto* pw = conv_ptr<const bf16>(o.wpk);
+  auto* py = conv_ptr<bf16>(o.y);
+  const bf16* pz = zero_page_bf16(o.x);
+  auto* ps = conv_ptr<const bf16>(o.skip);
+  const float* sc = o.scale.data_ptr<float>();
+  const float* sh = o.shift.data_ptr<float>();
+
+  if (SK == 1) {
+    if (has_skip)
+      hipLaunchKernelGGL((conv_fwd_bf16_64_kernel<false, true>), grid,
+          dim3(256), lds, s, px, pw, sc, sh, ps, pz, py, nullptr, Coutp64,
+          g, ksteps, kchunk, act);
+    else
+      hipLaunchKernelGGL((conv_fwd_bf16_64_kernel<false, false>), grid,
+          dim3(256), lds, s, px, pw, sc, sh, ps, pz, py, nullptr, Coutp64,
+          g, ksteps, kchunk, act);
+  } else {
+    auto part = torch::empty({(int64_t)SK * g.M * Coutp64},
+                             o.x.options().dtype(at::kFloat));
+    hipLaunchKernelGGL((conv_fwd_bf16_64_kernel<true, false>), grid,
+        dim3(256), lds, s, px, pw, sc, sh, nullptr, pz, py,
+        part.data_ptr<float>(), Coutp64, g, ksteps, kchunk, act);
+    const int64_t n = (int64_t)g.M * g.Cout;
+    if (has_skip)
+      hipLaunchKernelGGL((conv_splitk_reduce_kernel<true>),
+          dim3(ew_grid(n, 256)), dim3(256), 0, s, part.data_ptr<float>(),
+          sc, sh, ps, py, SK, Coutp64, g.Cout, (int64_t)g.M, act);
+    else
+      hipLaunchKernelGGL((conv_splitk_reduce_kernel<false>),
+          dim3(ew_grid(n, 256)), dim3(256), 0, s, part.data_ptr<float>(),
+          sc, sh, ps, py, SK, Coutp64, g.Cout, (int64_t)g.M, act);
+  }
+  HIP_CHECK_LAST();
+}
+
 torch::Tensor conv_fwd_small(torch::Tensor x, torch::Tensor wpk,
                              torch::Tensor scale, torch::Tensor shift,
                              c10::optional<torch::Tensor> skip,
                              int64_t KH, int64_t KW, int64_t stride,
                              int64_t pad, int64_t Cout, int64_t act,
                              int64_t splitk) {
-  auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   TORCH_CHECK(wpk.scalar_type() == at::kBFloat16,
               "conv_fwd_small: bf16 packed weights required");
-  if (xc.scalar_type() != at::kBFloat16) xc = xc.to(at::kBFloat16);
-  ConvGeoS g;
-  g.B = xc.size(0);
-  g.Cin = xc.size(1);
-  g.H = xc.size(2);
-  g.W = xc.size(3);
-  g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
-  g.Ho = (g.H + 2 * g.pad - (int)KH) / (int)stride + 1;
-  g.Wo = (g.W + 2 * g.pad - (int)KW) / (int)stride + 1;
-  g.Cout = Cout;
-  g.Cinp = (int)cdiv(g.Cin, 64) * 64;  // pack_weights 64-pad
-  g.Coutp = (int)cdiv(Cout, 128) * 128;  // pack_weights row padding
-  g.M = g.B * g.Ho * g.Wo;
-  g.nsteps = (int)(KH * KW) * (g.Cinp / 32);
-  TORCH_CHECK(g.Cin % 8 == 0, "conv_fwd_small: Cin % 8 required");
-  TORCH_CHECK(wpk.size(0) == KH * KW && wpk.size(1) == g.Coutp &&
-              wpk.size(2) == g.Cinp, "conv_fwd_small: packed weight shape");
-
-  int SK = (int)splitk;
-  if (SK < 1) SK = 1;
-  if (SK > g.nsteps) SK = g.nsteps;
-  g.chunk = (int)cdiv(g.nsteps, SK);
-  SK = (int)cdiv(g.nsteps, g.chunk);  // drop empty z-blocks
-
-  auto y = torch::empty({g.B, (int64_t)g.Cout, g.Ho, g.Wo},
-                        xc.options().memory_format(
-                            at::MemoryFormat::ChannelsLast));
-  auto sc = scale.to(at::kFloat).contiguous();
-  auto sh = shift.to(at::kFloat).contiguous();
-  const bool has_skip = skip.has_value();
-  torch::Tensor sk_t;
-  if (has_skip)
-    sk_t = skip->to(at::kBFloat16).contiguous(
-        at::MemoryFormat::ChannelsLast);
-
-  const int nblkN = (int)cdiv(Cout, 64);
-  const int Coutp64 = nblkN * 64;
-  dim3 grid(cdiv(g.M, 64), nblkN, SK);
-  auto s = at::cuda::getCurrentCUDAStream();
-  const size_t lds = 3 * 8192;
-
-  auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
-  auto* pw = reinterpret_cast<const bf16*>(wpk.data_ptr());
-  auto* py = reinterpret_cast<bf16*>(y.data_ptr());
-  const bf16* pz = zero_page_bf16(xc);
-  const bf16* ps =
-      has_skip ? reinterpret_cast<const bf16*>(sk_t.data_ptr()) : nullptr;
-
-  if (SK == 1) {
-    if (has_skip)
-      hipLaunchKernelGGL((conv_fwd_bf16_64_kernel<false, true>), grid,
-          dim3(256), lds, s, px, pw, sc.data_ptr<float>(),
-          sh.data_ptr<float>(), ps, pz, py, nullptr, Coutp64, g, (int)act);
-    else
-      hipLaunchKernelGGL((conv_fwd_bf16_64_kernel<false, false>), grid,
-          dim3(256), lds, s, px, pw, sc.data_ptr<float>(),
-          sh.data_ptr<float>(), ps, pz, py, nullptr, Coutp64, g, (int)act);
-  } else {
-    auto part = torch::empty({(int64_t)SK * g.M * Coutp64},
-                             xc.options().dtype(at::kFloat));
-    hipLaunchKernelGGL((conv_fwd_bf16_64_kernel<true, false>), grid,
-        dim3(256), lds, s, px, pw, sc.data_ptr<float>(),
-        sh.data_ptr<float>(), nullptr, pz, py, part.data_ptr<float>(),
-        Coutp64, g, (int)act);
-    const int64_t n = (int64_t)g.M * g.Cout;
-    if (has_skip)
-      hipLaunchKernelGGL((conv_splitk_reduce_kernel<true>),
-          dim3(ew_grid(n, 256)), dim3(256), 0, s, part.data_ptr<float>(),
-          sc.data_ptr<float>(), sh.data_ptr<float>(), ps, py, SK, Coutp64,
-          g.Cout, (int64_t)g.M, (int)act);
-    else
-      hipLaunchKernelGGL((conv_splitk_reduce_kernel<false>),
-          dim3(ew_grid(n, 256)), dim3(256), 0, s, part.data_ptr<float>(),
-          sc.data_ptr<float>(), sh.data_ptr<float>(), ps, py, SK, Coutp64,
-          g.Cout, (int64_t)g.M, (int)act);
-  }
-  HIP_CHECK_LAST();
-  return y;
+  const ConvGeo g = make_conv_geo("conv_fwd_small", x, wpk, KH, KW, stride,
+                                  pad, Cout, 64);
+  auto o = prep_conv_operands(g, x, wpk, scale, shift, skip, at::kBFloat16,
+                              at::kBFloat16);
+  launch_small(g, o, (int)act, (int)splitk);
+  return o.y;
 }
 
 }  // namespace rthd
