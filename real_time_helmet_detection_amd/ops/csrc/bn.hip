@@ -17,16 +17,67 @@
 // full rows (16 B/lane, no over-fetch — guide G13) and per-channel
 // parameters hoist out of the row loop. Requires octs = C/8 a power of two;
 // anything else falls back to the scalar generic path.
+//
+// Layout of this file: each mapping (scalar, octet) has ONE reduce skeleton
+// and ONE apply shell; what a kernel computes is a small functor handed to
+// the skeleton as its first argument.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <type_traits>
 #include "common.h"
 
 namespace rthd {
 
-DEV_INLINE float act_grad_from_pre(float pre, int act) {
-  if (act == ACT_RELU) return pre > 0.f ? 1.f : 0.f;
-  if (act == ACT_LRELU) return pre > 0.f ? 1.f : 0.01f;
-  return 1.f;
+// per-channel fp32 vectors every BN kernel reads
+struct BnParams {
+  const float *mean, *rstd, *gamma, *beta;
+};
+
+// The BN(+skip)+act backward expression tree, written once. The order —
+// (x-mu)*rsd, then xh*gm+bt, then +skip, then dy*act' — and the compiler's
+// default fp contraction of it are part of the kernels' bitwise contract.
+struct BnGrad {
+  float xh, pre, dpre;
+};
+
+template <bool HAS_SKIP>
+DEV_INLINE BnGrad bn_grad(float x, float mu, float rsd, float gm, float bt,
+                          float skip, float dy, int act) {
+  const float xh = (x - mu) * rsd;
+  float pre = xh * gm + bt;
+  if (HAS_SKIP) pre += skip;
+  return {xh, pre, dy * act_grad_by_sign(pre, act)};
+}
+
+// 16 B of bf16 <-> bf16[8]
+DEV_INLINE void ld8(bf16 (&v)[8], const bf16* p) {
+  *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(p);
+}
+DEV_INLINE void st8(bf16* p, const bf16 (&v)[8]) {
+  *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(v);
+}
+
+// the four parameter vectors of one channel octet, hoisted into registers
+struct BnOct {
+  float mu[8], rsd[8], gm[8], bt[8];
+};
+
+DEV_INLINE BnOct load_oct(const BnParams& p, int c0) {
+  BnOct o;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    o.mu[e] = p.mean[c0 + e];
+    o.rsd[e] = p.rstd[c0 + e];
+    o.gm[e] = p.gamma[c0 + e];
+    o.bt[e] = p.beta[c0 + e];
+  }
+  return o;
+}
+
+// fixed-order sum of the 4 sub-streams of a 64-channel x 4 block
+DEV_INLINE float sum4(const float* sh) {
+  return sh[threadIdx.x] + sh[threadIdx.x + 64] + sh[threadIdx.x + 128] +
+         sh[threadIdx.x + 192];
 }
 
 static bool fast8_ok(const torch::Tensor& t, int C) {
@@ -43,49 +94,133 @@ static int pick_chunks(int64_t M, int C) {
   return (int)chunks;
 }
 
-// --------------------- partial column sums (any C, scalar) -----------------
+// ----------------------------- reduce functors ------------------------------
+// Reduce functors add one element (scalar) or one octet row into two
+// accumulators; kTwo == false means the second sum does not exist (no LDS,
+// no work, no store).
 
 template <typename T, bool WANT_SQ>
-__global__ void colsum_part_kernel(const T* __restrict__ x,
-                                   float* __restrict__ psum,
-                                   float* __restrict__ psq,
-                                   int64_t M, int C) {
+struct ColSumElem {
+  static constexpr bool kTwo = WANT_SQ;
+  const T* x;
+  struct Ch {};
+  DEV_INLINE Ch channel(int) const { return {}; }
+  DEV_INLINE void add(const Ch&, int64_t i, float& s, float& ss) const {
+    const float v = ldf(&x[i]);
+    s += v;
+    if (WANT_SQ) ss += v * v;
+  }
+};
+
+template <bool WANT_SQ>
+struct ColSumRow8 {
+  static constexpr bool kTwo = WANT_SQ;
+  const bf16* x;
+  struct Ch {};
+  struct Row {
+    bf16 x[8];
+  };
+  DEV_INLINE Ch channel(int) const { return {}; }
+  DEV_INLINE void load(Row& v, int64_t i) const { ld8(v.x, x + i); }
+  DEV_INLINE void add(const Ch&, const Row& v, float (&acc)[8],
+                      float (&accsq)[8]) const {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float f = b2f(v.x[e]);
+      acc[e] += f;
+      if (WANT_SQ) accsq[e] += f * f;
+    }
+  }
+};
+
+// a1 = sum dpre (d_beta), a2 = sum dpre*xhat (d_gamma)
+template <typename T, bool HAS_SKIP>
+struct BnBwdElem {
+  static constexpr bool kTwo = true;
+  const T *dy, *x, *skip;
+  BnParams p;
+  int act;
+  struct Ch {
+    float mu, rsd, gm, bt;
+  };
+  DEV_INLINE Ch channel(int c) const {
+    return {p.mean[c], p.rstd[c], p.gamma[c], p.beta[c]};
+  }
+  DEV_INLINE void add(const Ch& ch, int64_t i, float& a1, float& a2) const {
+    const BnGrad g = bn_grad<HAS_SKIP>(
+        ldf(&x[i]), ch.mu, ch.rsd, ch.gm, ch.bt,
+        HAS_SKIP ? ldf(&skip[i]) : 0.f, ldf(&dy[i]), act);
+    a1 += g.dpre;
+    a2 += g.dpre * g.xh;
+  }
+};
+
+template <bool HAS_SKIP>
+struct BnBwdRow8 {
+  static constexpr bool kTwo = true;
+  const bf16 *dy, *x, *skip;
+  BnParams p;
+  int act;
+  using Ch = BnOct;
+  struct Row {
+    bf16 x[8], dy[8], skip[8];
+  };
+  DEV_INLINE Ch channel(int c0) const { return load_oct(p, c0); }
+  DEV_INLINE void load(Row& v, int64_t i) const {
+    ld8(v.x, x + i);
+    ld8(v.dy, dy + i);
+    if (HAS_SKIP) ld8(v.skip, skip + i);
+  }
+  DEV_INLINE void add(const Ch& ch, const Row& v, float (&a1)[8],
+                      float (&a2)[8]) const {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const BnGrad g = bn_grad<HAS_SKIP>(
+          b2f(v.x[e]), ch.mu[e], ch.rsd[e], ch.gm[e], ch.bt[e],
+          HAS_SKIP ? b2f(v.skip[e]) : 0.f, b2f(v.dy[e]), act);
+      a1[e] += g.dpre;
+      a2[e] += g.dpre * g.xh;
+    }
+  }
+};
+
+// --------------------------- reduce skeletons -------------------------------
+// Both: grid.y = row chunks; block y reduces rows [r0, r1) of every channel
+// it owns and stores one partial row p1[y][C] (and p2[y][C]).
+
+// scalar, any C: block = 64 channels x 4 row sub-streams, grid (C/64, chunks)
+template <typename F>
+__global__ void reduce_part_kernel(const F f, float* __restrict__ p1,
+                                   float* __restrict__ p2, int64_t M,
+                                   int C) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int sub = threadIdx.x >> 6;
   const bool live = c < C;
   const int64_t rows_per_chunk = (M + gridDim.y - 1) / gridDim.y;
   const int64_t r0 = blockIdx.y * rows_per_chunk;
   const int64_t r1 = min(M, r0 + rows_per_chunk);
-  float s = 0.f, ss = 0.f;
-  if (live)
-    for (int64_t r = r0 + sub; r < r1; r += 4) {
-      const float v = ldf(&x[r * C + c]);
-      s += v;
-      if (WANT_SQ) ss += v * v;
-    }
-  __shared__ float sh_s[256], sh_ss[256];
-  sh_s[threadIdx.x] = s;
-  if (WANT_SQ) sh_ss[threadIdx.x] = ss;
+  float a1 = 0.f, a2 = 0.f;
+  if (live) {
+    const typename F::Ch ch = f.channel(c);
+    for (int64_t r = r0 + sub; r < r1; r += 4) f.add(ch, r * C + c, a1, a2);
+  }
+  __shared__ float sh1[256], sh2[F::kTwo ? 256 : 1];
+  sh1[threadIdx.x] = a1;
+  if (F::kTwo) sh2[threadIdx.x] = a2;
   __syncthreads();
   if (sub == 0 && live) {
-    s = sh_s[threadIdx.x] + sh_s[threadIdx.x + 64] + sh_s[threadIdx.x + 128] +
-        sh_s[threadIdx.x + 192];
-    psum[(int64_t)blockIdx.y * C + c] = s;
-    if (WANT_SQ) {
-      ss = sh_ss[threadIdx.x] + sh_ss[threadIdx.x + 64] +
-           sh_ss[threadIdx.x + 128] + sh_ss[threadIdx.x + 192];
-      psq[(int64_t)blockIdx.y * C + c] = ss;
-    }
+    p1[(int64_t)blockIdx.y * C + c] = sum4(sh1);
+    if (F::kTwo) p2[(int64_t)blockIdx.y * C + c] = sum4(sh2);
   }
 }
 
-// ------------------ partial column sums (bf16 fast, C=8*2^k) ---------------
-
-template <bool WANT_SQ>
-__global__ void colsum8_part_kernel(const bf16* __restrict__ x,
-                                    float* __restrict__ psum,
-                                    float* __restrict__ psq,
-                                    int64_t M, int C) {
+// bf16 octets, C = 8*2^k: block = octs x streams threads, grid (1, chunks),
+// LDS halving tree over the streams. UNROLL rows are loaded before any is
+// consumed (independent 16-B loads in flight).
+template <int UNROLL, typename F>
+__global__ void reduce8_part_kernel(const F f, float* __restrict__ p1,
+                                    float* __restrict__ p2, int64_t M,
+                                    int C) {
   const int octs = C >> 3;
   const int streams = blockDim.x / octs;
   const int oct = threadIdx.x % octs;
@@ -94,51 +229,37 @@ __global__ void colsum8_part_kernel(const bf16* __restrict__ x,
   const int64_t rows_per_chunk = (M + gridDim.y - 1) / gridDim.y;
   const int64_t r0 = blockIdx.y * rows_per_chunk;
   const int64_t r1 = min(M, r0 + rows_per_chunk);
-  float acc[8] = {}, accsq[8] = {};
-  // 4x unrolled: one 16-B load per loop iteration leaves only ~4 MB in
-  // flight across the chip (< the ~6 MB needed to cover HBM latency at
-  // 8 TB/s); four independent loads per iteration saturate the bus.
+  const typename F::Ch ch = f.channel(c0);
+  float a1[8] = {}, a2[8] = {};
   int64_t r = r0 + rs;
-  for (; r + 3 * (int64_t)streams < r1; r += 4 * (int64_t)streams) {
-    bf16 v[4][8];
+  for (; r + (UNROLL - 1) * (int64_t)streams < r1;
+       r += UNROLL * (int64_t)streams) {
+    typename F::Row v[UNROLL];
 #pragma unroll
-    for (int u = 0; u < 4; ++u)
-      *reinterpret_cast<uint4*>(v[u]) = *reinterpret_cast<const uint4*>(
-          &x[(r + u * (int64_t)streams) * C + c0]);
+    for (int u = 0; u < UNROLL; ++u)
+      f.load(v[u], (r + u * (int64_t)streams) * C + c0);
 #pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float f = b2f(v[u][e]);
-        acc[e] += f;
-        if (WANT_SQ) accsq[e] += f * f;
-      }
+    for (int u = 0; u < UNROLL; ++u) f.add(ch, v[u], a1, a2);
   }
   for (; r < r1; r += streams) {
-    bf16 v[8];
-    *reinterpret_cast<uint4*>(v) =
-        *reinterpret_cast<const uint4*>(&x[r * C + c0]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float f = b2f(v[e]);
-      acc[e] += f;
-      if (WANT_SQ) accsq[e] += f * f;
-    }
+    typename F::Row v;
+    f.load(v, r * C + c0);
+    f.add(ch, v, a1, a2);
   }
-  __shared__ float sh[256][8];
-  __shared__ float shq[WANT_SQ ? 256 : 1][WANT_SQ ? 8 : 1];
+  __shared__ float sh1[256][8];
+  __shared__ float sh2[F::kTwo ? 256 : 1][F::kTwo ? 8 : 1];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) sh[threadIdx.x][e] = acc[e];
-  if (WANT_SQ)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) shq[threadIdx.x][e] = accsq[e];
+  for (int e = 0; e < 8; ++e) {
+    sh1[threadIdx.x][e] = a1[e];
+    if (F::kTwo) sh2[threadIdx.x][e] = a2[e];
+  }
   __syncthreads();
   for (int off = streams >> 1; off > 0; off >>= 1) {
     if (rs < off) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        sh[threadIdx.x][e] += sh[threadIdx.x + off * octs][e];
-        if (WANT_SQ) shq[threadIdx.x][e] += shq[threadIdx.x + off * octs][e];
+        sh1[threadIdx.x][e] += sh1[threadIdx.x + off * octs][e];
+        if (F::kTwo) sh2[threadIdx.x][e] += sh2[threadIdx.x + off * octs][e];
       }
     }
     __syncthreads();
@@ -146,12 +267,142 @@ __global__ void colsum8_part_kernel(const bf16* __restrict__ x,
   if (rs == 0) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      psum[(int64_t)blockIdx.y * C + c0 + e] = sh[threadIdx.x][e];
-      if (WANT_SQ)
-        psq[(int64_t)blockIdx.y * C + c0 + e] = shq[threadIdx.x][e];
+      p1[(int64_t)blockIdx.y * C + c0 + e] = sh1[threadIdx.x][e];
+      if (F::kTwo) p2[(int64_t)blockIdx.y * C + c0 + e] = sh2[threadIdx.x][e];
     }
   }
 }
+
+// ------------------------------ apply kernels -------------------------------
+// Forward and backward-apply share their mapping (scalar: grid-stride with
+// channel = i % C; octet: fixed octet per thread, rows gtid/octs + k*streams)
+// but stay four separate kernels: written as functors on a shared shell they
+// compile to different code. Pointers handed over inside a functor lose
+// __restrict__, and the scalar loops then no longer unroll (about 950 -> 270
+// instructions); the octet backward apply takes 90 instead of 79 VGPRs (one
+// wave/SIMD less) even when the shell is called with __restrict__ pointers.
+
+template <typename T, bool HAS_SKIP>
+__global__ void bn_act_fwd_kernel(const T* __restrict__ x,
+                                  const float* __restrict__ mean,
+                                  const float* __restrict__ rstd,
+                                  const float* __restrict__ gamma,
+                                  const float* __restrict__ beta,
+                                  const T* __restrict__ skip,
+                                  T* __restrict__ y, int64_t n, int C,
+                                  int act) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const int c = i % C;
+    const float xh = (ldf(&x[i]) - mean[c]) * rstd[c];
+    float pre = xh * gamma[c] + beta[c];
+    if (HAS_SKIP) pre += ldf(&skip[i]);
+    stf(&y[i], apply_act(pre, act));
+  }
+}
+
+// bf16 fast: fixed octet per thread -> per-channel params hoisted, here in
+// the folded scale/shift form (NOT the same expression as the scalar one)
+template <bool HAS_SKIP>
+__global__ void bn_act_fwd8_kernel(const bf16* __restrict__ x,
+                                   const float* __restrict__ mean,
+                                   const float* __restrict__ rstd,
+                                   const float* __restrict__ gamma,
+                                   const float* __restrict__ beta,
+                                   const bf16* __restrict__ skip,
+                                   bf16* __restrict__ y, int64_t M, int C,
+                                   int act) {
+  const int octs = C >> 3;
+  const int streams = (int)(((int64_t)blockDim.x * gridDim.y) / octs);
+  const int64_t gtid = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
+  const int oct = (int)(gtid % octs);
+  const int64_t rs = gtid / octs;
+  const int c0 = oct * 8;
+  float sc[8], sh[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float g = gamma[c0 + e] * rstd[c0 + e];
+    sc[e] = g;
+    sh[e] = beta[c0 + e] - mean[c0 + e] * g;
+  }
+  for (int64_t r = rs; r < M; r += streams) {
+    bf16 v[8], o[8], sk[8];
+    ld8(v, &x[r * C + c0]);
+    if (HAS_SKIP) ld8(sk, &skip[r * C + c0]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float pre = b2f(v[e]) * sc[e] + sh[e];
+      if (HAS_SKIP) pre += b2f(sk[e]);
+      o[e] = f2b(apply_act(pre, act));
+    }
+    st8(&y[r * C + c0], o);
+  }
+}
+
+// dx = gm*rsd*(dpre - s1/M - xhat*s2/M); dskip = dpre
+template <typename T, bool HAS_SKIP>
+__global__ void bn_act_bwd_apply_kernel(
+    const T* __restrict__ dy, const T* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ s1, const float* __restrict__ s2,
+    const T* __restrict__ skip, T* __restrict__ dskip,
+    T* __restrict__ dx, int64_t n, int C, float Mf, int act) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const int c = i % C;
+    const float mu = mean[c], rs = rstd[c], gm = gamma[c];
+    const BnGrad g = bn_grad<HAS_SKIP>(
+        ldf(&x[i]), mu, rs, gm, beta[c],
+        HAS_SKIP ? ldf(&skip[i]) : 0.f, ldf(&dy[i]), act);
+    if (HAS_SKIP) stf(&dskip[i], g.dpre);
+    stf(&dx[i], gm * rs * (g.dpre - s1[c] / Mf - g.xh * s2[c] / Mf));
+  }
+}
+
+template <bool HAS_SKIP>
+__global__ void bn_act_bwd_apply8_kernel(
+    const bf16* __restrict__ dy, const bf16* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ s1, const float* __restrict__ s2,
+    const bf16* __restrict__ skip, bf16* __restrict__ dskip,
+    bf16* __restrict__ dx, int64_t M, int C, float Mf, int act) {
+  const int octs = C >> 3;
+  const int streams = (int)(((int64_t)blockDim.x * gridDim.y) / octs);
+  const int64_t gtid = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
+  const int oct = (int)(gtid % octs);
+  const int64_t rs = gtid / octs;
+  const int c0 = oct * 8;
+  const float invM = 1.f / Mf;
+  const BnOct ch = load_oct({mean, rstd, gamma, beta}, c0);
+  float t1[8], t2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    t1[e] = s1[c0 + e] * invM;
+    t2[e] = s2[c0 + e] * invM;
+  }
+  for (int64_t r = rs; r < M; r += streams) {
+    bf16 vx[8], vdy[8], o[8], vsk[8], osk[8];
+    ld8(vx, &x[r * C + c0]);
+    ld8(vdy, &dy[r * C + c0]);
+    if (HAS_SKIP) ld8(vsk, &skip[r * C + c0]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const BnGrad g = bn_grad<HAS_SKIP>(
+          b2f(vx[e]), ch.mu[e], ch.rsd[e], ch.gm[e], ch.bt[e],
+          HAS_SKIP ? b2f(vsk[e]) : 0.f, b2f(vdy[e]), act);
+      if (HAS_SKIP) osk[e] = f2b(g.dpre);
+      o[e] = f2b(ch.gm[e] * ch.rsd[e] * (g.dpre - t1[e] - g.xh * t2[e]));
+    }
+    if (HAS_SKIP) st8(&dskip[r * C + c0], osk);
+    st8(&dx[r * C + c0], o);
+  }
+}
+
+// ------------------ deterministic finish of [chunks][C] partials ------------
 
 // stage1[ks][c] = sum of the ks-th K-slice of p[k][c] (and stage2/p2).
 // block = 64 channels x 4 k-substreams (a K=256 serial loop in one tiny
@@ -180,14 +431,8 @@ __global__ void reduce_partials_kernel(const float* __restrict__ p1,
   shb[threadIdx.x] = b;
   __syncthreads();
   if (sub == 0 && c < C) {
-    a = sha[threadIdx.x] + sha[threadIdx.x + 64] + sha[threadIdx.x + 128] +
-        sha[threadIdx.x + 192];
-    o1[(int64_t)blockIdx.y * C + c] = a;
-    if (p2) {
-      b = shb[threadIdx.x] + shb[threadIdx.x + 64] + shb[threadIdx.x + 128] +
-          shb[threadIdx.x + 192];
-      o2[(int64_t)blockIdx.y * C + c] = b;
-    }
+    o1[(int64_t)blockIdx.y * C + c] = sum4(sha);
+    if (p2) o2[(int64_t)blockIdx.y * C + c] = sum4(shb);
   }
 }
 
@@ -227,7 +472,8 @@ __global__ void reduce_final_kernel(const float* __restrict__ s1,
   }
 }
 
-// staged two-kernel deterministic reduction of [chunks][C] partials
+// --------------------------------- host -------------------------------------
+
 struct BnFinalize {
   float* mean = nullptr;
   float* rstd = nullptr;
@@ -236,17 +482,39 @@ struct BnFinalize {
   float Mf = 1.f, momentum = 0.1f, eps = 1e-5f;
 };
 
+static BnFinalize make_finalize(torch::Tensor& mean, torch::Tensor& rstd,
+                                c10::optional<torch::Tensor>& running_mean,
+                                c10::optional<torch::Tensor>& running_var,
+                                int64_t M, double momentum, double eps) {
+  BnFinalize fin;
+  fin.mean = mean.data_ptr<float>();
+  fin.rstd = rstd.data_ptr<float>();
+  if (running_mean.has_value()) {
+    TORCH_CHECK(running_mean->scalar_type() == at::kFloat);
+    fin.run_mean = running_mean->data_ptr<float>();
+    fin.run_var = running_var->data_ptr<float>();
+  }
+  fin.Mf = (float)M;
+  fin.momentum = (float)momentum;
+  fin.eps = (float)eps;
+  return fin;
+}
+
+// staged two-kernel deterministic reduction of [chunks][C] partials
 static void run_reduce_partials(const float* p1, const float* p2,
                                 float* o1, float* o2, int chunks, int C,
                                 const torch::TensorOptions& opt,
                                 hipStream_t s,
                                 const BnFinalize& fin = BnFinalize{}) {
+  auto finish = [&](const float* s1, const float* s2, int K) {
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(cdiv(C, 256)), dim3(256),
+        0, s, s1, s2, o1, o2, K, C, fin.mean, fin.rstd, fin.run_mean,
+        fin.run_var, fin.Mf, fin.momentum, fin.eps);
+  };
   if (chunks <= 8) {
     // stage 1 would be a pure copy (each y-block owns exactly one row):
     // reduce the partials directly in fixed order
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(cdiv(C, 256)), dim3(256),
-        0, s, p1, p2, o1, o2, chunks, C, fin.mean, fin.rstd, fin.run_mean,
-        fin.run_var, fin.Mf, fin.momentum, fin.eps);
+    finish(p1, p2, chunks);
     return;
   }
   // ks sets BOTH stage-1 parallelism and the single-block stage-2 loop
@@ -261,299 +529,62 @@ static void run_reduce_partials(const float* p1, const float* p2,
   float* s2 = p2 ? s1 + (int64_t)ks * C : nullptr;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3(cdiv(C, 64), ks),
       dim3(256), 0, s, p1, p2, s1, s2, chunks, C);
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(cdiv(C, 256)), dim3(256),
-      0, s, s1, s2, o1, o2, ks, C, fin.mean, fin.rstd, fin.run_mean,
-      fin.run_var, fin.Mf, fin.momentum, fin.eps);
+  finish(s1, s2, ks);
 }
 
+// runtime bool / dtype -> compile-time argument of a generic lambda
+template <typename Fn>
+static void with_bool(bool b, Fn&& fn) {
+  if (b) fn(std::true_type{});
+  else fn(std::false_type{});
+}
 
-// ---------------------------- bn apply forward ------------------------------
+template <typename T>
+struct TypeTag {
+  using type = T;
+};
 
-template <typename T, bool HAS_SKIP>
-__global__ void bn_act_fwd_kernel(const T* __restrict__ x,
-                                  const float* __restrict__ mean,
-                                  const float* __restrict__ rstd,
-                                  const float* __restrict__ gamma,
-                                  const float* __restrict__ beta,
-                                  const T* __restrict__ skip,
-                                  T* __restrict__ y, int64_t n, int C,
-                                  int act) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const int c = i % C;
-    const float xh = (ldf(&x[i]) - mean[c]) * rstd[c];
-    float pre = xh * gamma[c] + beta[c];
-    if (HAS_SKIP) pre += ldf(&skip[i]);
-    stf(&y[i], apply_act(pre, act));
+template <typename Fn>
+static void with_dtype(const torch::Tensor& t, Fn&& fn) {
+  if (t.scalar_type() == at::kBFloat16) {
+    fn(TypeTag<bf16>{});
+  } else {
+    TORCH_CHECK(t.scalar_type() == at::kFloat, "bf16/f32 only");
+    fn(TypeTag<float>{});
   }
 }
 
-// bf16 fast: fixed octet per thread -> per-channel params hoisted
-template <bool HAS_SKIP>
-__global__ void bn_act_fwd8_kernel(const bf16* __restrict__ x,
-                                   const float* __restrict__ mean,
-                                   const float* __restrict__ rstd,
-                                   const float* __restrict__ gamma,
-                                   const float* __restrict__ beta,
-                                   const bf16* __restrict__ skip,
-                                   bf16* __restrict__ y, int64_t M, int C,
-                                   int act) {
-  const int octs = C >> 3;
-  const int streams = (int)(((int64_t)blockDim.x * gridDim.y) / octs);
-  const int64_t gtid = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
-  const int oct = (int)(gtid % octs);
-  const int64_t rs = gtid / octs;
-  const int c0 = oct * 8;
-  float sc[8], sh[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float g = gamma[c0 + e] * rstd[c0 + e];
-    sc[e] = g;
-    sh[e] = beta[c0 + e] - mean[c0 + e] * g;
-  }
-  for (int64_t r = rs; r < M; r += streams) {
-    bf16 v[8], o[8], sk[8];
-    *reinterpret_cast<uint4*>(v) =
-        *reinterpret_cast<const uint4*>(&x[r * C + c0]);
-    if (HAS_SKIP)
-      *reinterpret_cast<uint4*>(sk) =
-          *reinterpret_cast<const uint4*>(&skip[r * C + c0]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float pre = b2f(v[e]) * sc[e] + sh[e];
-      if (HAS_SKIP) pre += b2f(sk[e]);
-      o[e] = f2b(apply_act(pre, act));
-    }
-    *reinterpret_cast<uint4*>(&y[r * C + c0]) = *reinterpret_cast<uint4*>(o);
-  }
+// typed data pointer; nullptr for an undefined (absent) tensor
+template <typename T>
+static T* ptr(const torch::Tensor& t) {
+  return t.defined() ? reinterpret_cast<T*>(t.data_ptr()) : nullptr;
 }
 
-// ---------------------------- bn backward -----------------------------------
-
-template <typename T, bool HAS_SKIP>
-__global__ void bn_bwd_reduce_part_kernel(
-    const T* __restrict__ dy, const T* __restrict__ x,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    const float* __restrict__ gamma, const float* __restrict__ beta,
-    const T* __restrict__ skip,
-    float* __restrict__ p1, float* __restrict__ p2,
-    int64_t M, int C, int act) {
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int sub = threadIdx.x >> 6;
-  const bool live = c < C;
-  const int64_t rows_per_chunk = (M + gridDim.y - 1) / gridDim.y;
-  const int64_t r0 = blockIdx.y * rows_per_chunk;
-  const int64_t r1 = live ? min(M, r0 + rows_per_chunk) : r0;
-  const float mu = live ? mean[c] : 0.f;
-  const float rsd = live ? rstd[c] : 0.f;
-  const float gm = live ? gamma[c] : 0.f;
-  const float bt = live ? beta[c] : 0.f;
-  float a1 = 0.f, a2 = 0.f;
-  for (int64_t r = r0 + sub; r < r1; r += 4) {
-    const float xh = (ldf(&x[r * C + c]) - mu) * rsd;
-    float pre = xh * gm + bt;
-    if (HAS_SKIP) pre += ldf(&skip[r * C + c]);
-    const float dpre = ldf(&dy[r * C + c]) * act_grad_from_pre(pre, act);
-    a1 += dpre;
-    a2 += dpre * xh;
-  }
-  __shared__ float sh1[256], sh2[256];
-  sh1[threadIdx.x] = a1;
-  sh2[threadIdx.x] = a2;
-  __syncthreads();
-  if (sub == 0 && live) {
-    a1 = sh1[threadIdx.x] + sh1[threadIdx.x + 64] + sh1[threadIdx.x + 128] +
-         sh1[threadIdx.x + 192];
-    a2 = sh2[threadIdx.x] + sh2[threadIdx.x + 64] + sh2[threadIdx.x + 128] +
-         sh2[threadIdx.x + 192];
-    p1[(int64_t)blockIdx.y * C + c] = a1;
-    p2[(int64_t)blockIdx.y * C + c] = a2;
-  }
+static BnParams bn_params(const torch::Tensor& mean, const torch::Tensor& rstd,
+                          const torch::Tensor& gm, const torch::Tensor& bt) {
+  return {mean.data_ptr<float>(), rstd.data_ptr<float>(),
+          gm.data_ptr<float>(), bt.data_ptr<float>()};
 }
 
-template <bool HAS_SKIP>
-__global__ void bn_bwd_reduce8_part_kernel(
-    const bf16* __restrict__ dy, const bf16* __restrict__ x,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    const float* __restrict__ gamma, const float* __restrict__ beta,
-    const bf16* __restrict__ skip,
-    float* __restrict__ p1, float* __restrict__ p2,
-    int64_t M, int C, int act) {
-  const int octs = C >> 3;
-  const int streams = blockDim.x / octs;
-  const int oct = threadIdx.x % octs;
-  const int rs = threadIdx.x / octs;
-  const int c0 = oct * 8;
-  const int64_t rows_per_chunk = (M + gridDim.y - 1) / gridDim.y;
-  const int64_t r0 = blockIdx.y * rows_per_chunk;
-  const int64_t r1 = min(M, r0 + rows_per_chunk);
-  float mu[8], rsd[8], gm[8], bt[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    mu[e] = mean[c0 + e];
-    rsd[e] = rstd[c0 + e];
-    gm[e] = gamma[c0 + e];
-    bt[e] = beta[c0 + e];
-  }
-  float a1[8] = {}, a2[8] = {};
-  // 2x unrolled (2-3 loads/iter already): 4-6 independent loads in flight
-  // (4x was measured SLOWER: 71 -> 98 us — register pressure)
-  int64_t r = r0 + rs;
-  for (; r + (int64_t)streams < r1; r += 2 * (int64_t)streams) {
-    bf16 vx[2][8], vdy[2][8], vsk[2][8];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int64_t rr = (r + u * (int64_t)streams) * C + c0;
-      *reinterpret_cast<uint4*>(vx[u]) =
-          *reinterpret_cast<const uint4*>(&x[rr]);
-      *reinterpret_cast<uint4*>(vdy[u]) =
-          *reinterpret_cast<const uint4*>(&dy[rr]);
-      if (HAS_SKIP)
-        *reinterpret_cast<uint4*>(vsk[u]) =
-            *reinterpret_cast<const uint4*>(&skip[rr]);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float xh = (b2f(vx[u][e]) - mu[e]) * rsd[e];
-        float pre = xh * gm[e] + bt[e];
-        if (HAS_SKIP) pre += b2f(vsk[u][e]);
-        const float dpre = b2f(vdy[u][e]) * act_grad_from_pre(pre, act);
-        a1[e] += dpre;
-        a2[e] += dpre * xh;
-      }
-  }
-  for (; r < r1; r += streams) {
-    bf16 vx[8], vdy[8], vsk[8];
-    *reinterpret_cast<uint4*>(vx) =
-        *reinterpret_cast<const uint4*>(&x[r * C + c0]);
-    *reinterpret_cast<uint4*>(vdy) =
-        *reinterpret_cast<const uint4*>(&dy[r * C + c0]);
-    if (HAS_SKIP)
-      *reinterpret_cast<uint4*>(vsk) =
-          *reinterpret_cast<const uint4*>(&skip[r * C + c0]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float xh = (b2f(vx[e]) - mu[e]) * rsd[e];
-      float pre = xh * gm[e] + bt[e];
-      if (HAS_SKIP) pre += b2f(vsk[e]);
-      const float dpre = b2f(vdy[e]) * act_grad_from_pre(pre, act);
-      a1[e] += dpre;
-      a2[e] += dpre * xh;
-    }
-  }
-  __shared__ float sh1[256][8], sh2[256][8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    sh1[threadIdx.x][e] = a1[e];
-    sh2[threadIdx.x][e] = a2[e];
-  }
-  __syncthreads();
-  for (int off = streams >> 1; off > 0; off >>= 1) {
-    if (rs < off) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        sh1[threadIdx.x][e] += sh1[threadIdx.x + off * octs][e];
-        sh2[threadIdx.x][e] += sh2[threadIdx.x + off * octs][e];
-      }
-    }
-    __syncthreads();
-  }
-  if (rs == 0) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      p1[(int64_t)blockIdx.y * C + c0 + e] = sh1[threadIdx.x][e];
-      p2[(int64_t)blockIdx.y * C + c0 + e] = sh2[threadIdx.x][e];
-    }
-  }
+// one launch site per reduce skeleton
+template <typename F>
+static void launch_reduce(const F& f, float* p1, float* p2, int chunks,
+                          int64_t M, int C, hipStream_t s) {
+  hipLaunchKernelGGL((reduce_part_kernel<F>), dim3(cdiv(C, 64), chunks),
+      dim3(256), 0, s, f, p1, p2, M, C);
 }
 
-template <typename T, bool HAS_SKIP>
-__global__ void bn_act_bwd_apply_kernel(
-    const T* __restrict__ dy, const T* __restrict__ x,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ s1, const float* __restrict__ s2,
-    const T* __restrict__ skip, T* __restrict__ dskip,
-    T* __restrict__ dx, int64_t n, int C, float Mf, int act) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    const int c = i % C;
-    const float mu = mean[c], rs = rstd[c], gm = gamma[c];
-    const float xh = (ldf(&x[i]) - mu) * rs;
-    float pre = xh * gm + beta[c];
-    if (HAS_SKIP) pre += ldf(&skip[i]);
-    const float dpre = ldf(&dy[i]) * act_grad_from_pre(pre, act);
-    if (HAS_SKIP) stf(&dskip[i], dpre);
-    stf(&dx[i], gm * rs * (dpre - s1[c] / Mf - xh * s2[c] / Mf));
-  }
+template <int UNROLL, typename F>
+static void launch_reduce8(const F& f, float* p1, float* p2, int chunks,
+                           int64_t M, int C, hipStream_t s) {
+  hipLaunchKernelGGL((reduce8_part_kernel<UNROLL, F>), dim3(1, chunks),
+      dim3(256), 0, s, f, p1, p2, M, C);
 }
 
-template <bool HAS_SKIP>
-__global__ void bn_act_bwd_apply8_kernel(
-    const bf16* __restrict__ dy, const bf16* __restrict__ x,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ s1, const float* __restrict__ s2,
-    const bf16* __restrict__ skip, bf16* __restrict__ dskip,
-    bf16* __restrict__ dx, int64_t M, int C, float Mf, int act) {
-  const int octs = C >> 3;
-  const int streams = (int)(((int64_t)blockDim.x * gridDim.y) / octs);
-  const int64_t gtid = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
-  const int oct = (int)(gtid % octs);
-  const int64_t rs = gtid / octs;
-  const int c0 = oct * 8;
-  const float invM = 1.f / Mf;
-  float mu[8], rsd[8], gm[8], bt[8], t1[8], t2[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    mu[e] = mean[c0 + e];
-    rsd[e] = rstd[c0 + e];
-    gm[e] = gamma[c0 + e];
-    bt[e] = beta[c0 + e];
-    t1[e] = s1[c0 + e] * invM;
-    t2[e] = s2[c0 + e] * invM;
-  }
-  for (int64_t r = rs; r < M; r += streams) {
-    bf16 vx[8], vdy[8], o[8], vsk[8], osk[8];
-    *reinterpret_cast<uint4*>(vx) =
-        *reinterpret_cast<const uint4*>(&x[r * C + c0]);
-    *reinterpret_cast<uint4*>(vdy) =
-        *reinterpret_cast<const uint4*>(&dy[r * C + c0]);
-    if (HAS_SKIP)
-      *reinterpret_cast<uint4*>(vsk) =
-          *reinterpret_cast<const uint4*>(&skip[r * C + c0]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float xh = (b2f(vx[e]) - mu[e]) * rsd[e];
-      float pre = xh * gm[e] + bt[e];
-      if (HAS_SKIP) pre += b2f(vsk[e]);
-      const float dpre = b2f(vdy[e]) * act_grad_from_pre(pre, act);
-      if (HAS_SKIP) osk[e] = f2b(dpre);
-      o[e] = f2b(gm[e] * rsd[e] * (dpre - t1[e] - xh * t2[e]));
-    }
-    if (HAS_SKIP)
-      *reinterpret_cast<uint4*>(&dskip[r * C + c0]) =
-          *reinterpret_cast<uint4*>(osk);
-    *reinterpret_cast<uint4*>(&dx[r * C + c0]) =
-        *reinterpret_cast<uint4*>(o);
-  }
+// grid of the octet apply kernels: (1, nb) blocks of 256
+static int rows8_blocks(int64_t M, int C) {
+  return (int)std::min<int64_t>(cdiv(M * (C / 8), 256), 2048);
 }
-
-// --------------------------------- wrappers ---------------------------------
-
-#define DT(tensor, body)                                                     \
-  if ((tensor).scalar_type() == at::kBFloat16) {                             \
-    using scalar_t = bf16;                                                   \
-    body                                                                     \
-  } else {                                                                   \
-    TORCH_CHECK((tensor).scalar_type() == at::kFloat, "bf16/f32 only");      \
-    using scalar_t = float;                                                  \
-    body                                                                     \
-  }
 
 static void run_colsum(const torch::Tensor& xc, torch::Tensor& sum,
                        torch::Tensor* sumsq, int64_t M, int C,
@@ -562,33 +593,27 @@ static void run_colsum(const torch::Tensor& xc, torch::Tensor& sum,
   const int chunks = pick_chunks(M, C);
   auto p1 = torch::empty({chunks, C}, sum.options());
   torch::Tensor p2;
-  float* p2p = nullptr;
-  if (sumsq) {
-    p2 = torch::empty({chunks, C}, sum.options());
-    p2p = p2.data_ptr<float>();
-  }
-  if (fast8_ok(xc, C)) {
-    auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
-    if (sumsq)
-      hipLaunchKernelGGL((colsum8_part_kernel<true>), dim3(1, chunks),
-          dim3(256), 0, s, px, p1.data_ptr<float>(), p2p, M, C);
-    else
-      hipLaunchKernelGGL((colsum8_part_kernel<false>), dim3(1, chunks),
-          dim3(256), 0, s, px, p1.data_ptr<float>(), p2p, M, C);
-  } else {
-    DT(xc, {
-      auto* px = reinterpret_cast<const scalar_t*>(xc.data_ptr());
-      if (sumsq)
-        hipLaunchKernelGGL((colsum_part_kernel<scalar_t, true>),
-            dim3(cdiv(C, 64), chunks), dim3(256), 0, s, px,
-            p1.data_ptr<float>(), p2p, M, C);
-      else
-        hipLaunchKernelGGL((colsum_part_kernel<scalar_t, false>),
-            dim3(cdiv(C, 64), chunks), dim3(256), 0, s, px,
-            p1.data_ptr<float>(), p2p, M, C);
-    });
-  }
-  run_reduce_partials(p1.data_ptr<float>(), p2p, sum.data_ptr<float>(),
+  if (sumsq) p2 = torch::empty({chunks, C}, sum.options());
+  float* p1p = p1.data_ptr<float>();
+  float* p2p = ptr<float>(p2);
+  const bool fast8 = fast8_ok(xc, C);
+  with_bool(sumsq != nullptr, [&](auto want_sq) {
+    constexpr bool SQ = decltype(want_sq)::value;
+    if (fast8) {
+      // 4x unrolled: one 16-B load per loop iteration leaves only ~4 MB in
+      // flight across the chip (< the ~6 MB needed to cover HBM latency at
+      // 8 TB/s); four independent loads per iteration saturate the bus.
+      launch_reduce8<4>(ColSumRow8<SQ>{ptr<const bf16>(xc)}, p1p, p2p,
+                        chunks, M, C, s);
+    } else {
+      with_dtype(xc, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        launch_reduce(ColSumElem<T, SQ>{ptr<const T>(xc)}, p1p, p2p, chunks,
+                      M, C, s);
+      });
+    }
+  });
+  run_reduce_partials(p1p, p2p, sum.data_ptr<float>(),
                       sumsq ? sumsq->data_ptr<float>() : nullptr, chunks,
                       C, sum.options(), s, fin);
 }
@@ -606,18 +631,9 @@ std::vector<torch::Tensor> bn_stats(torch::Tensor x,
   auto mean = torch::empty({C}, xc.options().dtype(at::kFloat));
   auto rstd = torch::empty({C}, xc.options().dtype(at::kFloat));
   auto s = at::cuda::getCurrentCUDAStream();
-  BnFinalize fin;
-  fin.mean = mean.data_ptr<float>();
-  fin.rstd = rstd.data_ptr<float>();
-  if (running_mean.has_value()) {
-    TORCH_CHECK(running_mean->scalar_type() == at::kFloat);
-    fin.run_mean = running_mean->data_ptr<float>();
-    fin.run_var = running_var->data_ptr<float>();
-  }
-  fin.Mf = (float)M;
-  fin.momentum = (float)momentum;
-  fin.eps = (float)eps;
-  run_colsum(xc, sum, &sumsq, M, C, s, fin);  // finalize fused in
+  run_colsum(xc, sum, &sumsq, M, C, s,  // finalize fused in
+             make_finalize(mean, rstd, running_mean, running_var, M,
+                           momentum, eps));
   HIP_CHECK_LAST();
   return {mean, rstd};
 }
@@ -640,20 +656,11 @@ std::vector<torch::Tensor> bn_stats_from_parts(
   auto mean = torch::empty({C}, opt);
   auto rstd = torch::empty({C}, opt);
   auto s = at::cuda::getCurrentCUDAStream();
-  BnFinalize fin;
-  fin.mean = mean.data_ptr<float>();
-  fin.rstd = rstd.data_ptr<float>();
-  if (running_mean.has_value()) {
-    TORCH_CHECK(running_mean->scalar_type() == at::kFloat);
-    fin.run_mean = running_mean->data_ptr<float>();
-    fin.run_var = running_var->data_ptr<float>();
-  }
-  fin.Mf = (float)M;
-  fin.momentum = (float)momentum;
-  fin.eps = (float)eps;
   run_reduce_partials(p1.data_ptr<float>(), p2.data_ptr<float>(),
                       sum.data_ptr<float>(), sumsq.data_ptr<float>(),
-                      chunks, C, opt, s, fin);
+                      chunks, C, opt, s,
+                      make_finalize(mean, rstd, running_mean, running_var,
+                                    M, momentum, eps));
   HIP_CHECK_LAST();
   return {mean, rstd};
 }
@@ -674,43 +681,23 @@ torch::Tensor bn_act_fwd(torch::Tensor x, torch::Tensor mean,
   torch::Tensor sk;
   if (has_skip)
     sk = skip->to(xc.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
-  if (fast8_ok(xc, C)) {
-    const int octs = C / 8;
-    const int nb = (int)std::min<int64_t>(cdiv(M * octs, 256), 2048);
-    auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
-    auto* py = reinterpret_cast<bf16*>(y.data_ptr());
-    const bf16* ps = has_skip
-        ? reinterpret_cast<const bf16*>(sk.data_ptr()) : nullptr;
-    if (has_skip)
-      hipLaunchKernelGGL((bn_act_fwd8_kernel<true>), dim3(1, nb), dim3(256),
-          0, s, px, mean.data_ptr<float>(), rstd.data_ptr<float>(),
-          gm.data_ptr<float>(), bt.data_ptr<float>(), ps, py, M, C,
-          (int)act);
-    else
-      hipLaunchKernelGGL((bn_act_fwd8_kernel<false>), dim3(1, nb), dim3(256),
-          0, s, px, mean.data_ptr<float>(), rstd.data_ptr<float>(),
-          gm.data_ptr<float>(), bt.data_ptr<float>(), ps, py, M, C,
-          (int)act);
-  } else {
-    DT(xc, {
-      auto* px = reinterpret_cast<const scalar_t*>(xc.data_ptr());
-      auto* py = reinterpret_cast<scalar_t*>(y.data_ptr());
-      const scalar_t* ps = has_skip
-          ? reinterpret_cast<const scalar_t*>(sk.data_ptr()) : nullptr;
-      if (has_skip)
-        hipLaunchKernelGGL((bn_act_fwd_kernel<scalar_t, true>),
-            dim3(ew_grid(n, 256)), dim3(256), 0, s, px,
-            mean.data_ptr<float>(), rstd.data_ptr<float>(),
-            gm.data_ptr<float>(), bt.data_ptr<float>(), ps, py, n, C,
-            (int)act);
-      else
-        hipLaunchKernelGGL((bn_act_fwd_kernel<scalar_t, false>),
-            dim3(ew_grid(n, 256)), dim3(256), 0, s, px,
-            mean.data_ptr<float>(), rstd.data_ptr<float>(),
-            gm.data_ptr<float>(), bt.data_ptr<float>(), ps, py, n, C,
-            (int)act);
-    });
-  }
+  const BnParams p = bn_params(mean, rstd, gm, bt);
+  const bool fast8 = fast8_ok(xc, C);
+  with_bool(has_skip, [&](auto hs) {
+    constexpr bool HS = decltype(hs)::value;
+    if (fast8) {
+      hipLaunchKernelGGL((bn_act_fwd8_kernel<HS>), dim3(1, rows8_blocks(M, C)),
+          dim3(256), 0, s, ptr<const bf16>(xc), p.mean, p.rstd, p.gamma,
+          p.beta, ptr<const bf16>(sk), ptr<bf16>(y), M, C, (int)act);
+    } else {
+      with_dtype(xc, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((bn_act_fwd_kernel<T, HS>), dim3(ew_grid(n, 256)),
+            dim3(256), 0, s, ptr<const T>(xc), p.mean, p.rstd, p.gamma,
+            p.beta, ptr<const T>(sk), ptr<T>(y), n, C, (int)act);
+      });
+    }
+  });
   HIP_CHECK_LAST();
   return y;
 }
@@ -741,96 +728,48 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
   const int chunks = pick_chunks(M, C);
   auto p1 = torch::empty({chunks, C}, s1.options());
   auto p2 = torch::empty({chunks, C}, s1.options());
-  if (fast8_ok(xc, C)) {
-    auto* pdy = reinterpret_cast<const bf16*>(dyc.data_ptr());
-    auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
-    const bf16* ps = has_skip
-        ? reinterpret_cast<const bf16*>(sk.data_ptr()) : nullptr;
-    if (has_skip)
-      hipLaunchKernelGGL((bn_bwd_reduce8_part_kernel<true>), dim3(1, chunks),
-          dim3(256), 0, s, pdy, px,
-          mean.data_ptr<float>(), rstd.data_ptr<float>(),
-          gm.data_ptr<float>(), bt.data_ptr<float>(), ps,
-          p1.data_ptr<float>(), p2.data_ptr<float>(), M, C, (int)act);
-    else
-      hipLaunchKernelGGL((bn_bwd_reduce8_part_kernel<false>),
-          dim3(1, chunks), dim3(256), 0, s, pdy, px,
-          mean.data_ptr<float>(), rstd.data_ptr<float>(),
-          gm.data_ptr<float>(), bt.data_ptr<float>(), ps,
-          p1.data_ptr<float>(), p2.data_ptr<float>(), M, C, (int)act);
-  } else {
-    DT(xc, {
-      auto* pdy = reinterpret_cast<const scalar_t*>(dyc.data_ptr());
-      auto* px = reinterpret_cast<const scalar_t*>(xc.data_ptr());
-      const scalar_t* ps = has_skip
-          ? reinterpret_cast<const scalar_t*>(sk.data_ptr()) : nullptr;
-      if (has_skip)
-        hipLaunchKernelGGL((bn_bwd_reduce_part_kernel<scalar_t, true>),
-            dim3(cdiv(C, 64), chunks), dim3(256), 0, s, pdy, px,
-            mean.data_ptr<float>(), rstd.data_ptr<float>(),
-            gm.data_ptr<float>(), bt.data_ptr<float>(), ps,
-            p1.data_ptr<float>(), p2.data_ptr<float>(), M, C, (int)act);
-      else
-        hipLaunchKernelGGL((bn_bwd_reduce_part_kernel<scalar_t, false>),
-            dim3(cdiv(C, 64), chunks), dim3(256), 0, s, pdy, px,
-            mean.data_ptr<float>(), rstd.data_ptr<float>(),
-            gm.data_ptr<float>(), bt.data_ptr<float>(), ps,
-            p1.data_ptr<float>(), p2.data_ptr<float>(), M, C, (int)act);
-    });
-  }
-  run_reduce_partials(p1.data_ptr<float>(), p2.data_ptr<float>(),
-                      s1.data_ptr<float>(), s2.data_ptr<float>(), chunks,
-                      C, s1.options(), s);
-
-  if (fast8_ok(xc, C)) {
-    const int octs = C / 8;
-    const int nb = (int)std::min<int64_t>(cdiv(M * octs, 256), 2048);
-    auto* pdy = reinterpret_cast<const bf16*>(dyc.data_ptr());
-    auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
-    auto* pdx = reinterpret_cast<bf16*>(dx.data_ptr());
-    const bf16* ps = has_skip
-        ? reinterpret_cast<const bf16*>(sk.data_ptr()) : nullptr;
-    bf16* pdsk = has_skip
-        ? reinterpret_cast<bf16*>(dsk.data_ptr()) : nullptr;
-    if (has_skip)
-      hipLaunchKernelGGL((bn_act_bwd_apply8_kernel<true>), dim3(1, nb),
-          dim3(256), 0, s, pdy, px,
-          mean.data_ptr<float>(), rstd.data_ptr<float>(),
-          gm.data_ptr<float>(), bt.data_ptr<float>(),
-          s1.data_ptr<float>(), s2.data_ptr<float>(), ps, pdsk, pdx, M, C,
-          (float)M, (int)act);
-    else
-      hipLaunchKernelGGL((bn_act_bwd_apply8_kernel<false>), dim3(1, nb),
-          dim3(256), 0, s, pdy, px,
-          mean.data_ptr<float>(), rstd.data_ptr<float>(),
-          gm.data_ptr<float>(), bt.data_ptr<float>(),
-          s1.data_ptr<float>(), s2.data_ptr<float>(), ps, pdsk, pdx, M, C,
-          (float)M, (int)act);
-  } else {
-    DT(xc, {
-      auto* pdy = reinterpret_cast<const scalar_t*>(dyc.data_ptr());
-      auto* px = reinterpret_cast<const scalar_t*>(xc.data_ptr());
-      auto* pdx = reinterpret_cast<scalar_t*>(dx.data_ptr());
-      const scalar_t* ps = has_skip
-          ? reinterpret_cast<const scalar_t*>(sk.data_ptr()) : nullptr;
-      scalar_t* pdsk = has_skip
-          ? reinterpret_cast<scalar_t*>(dsk.data_ptr()) : nullptr;
-      if (has_skip)
-        hipLaunchKernelGGL((bn_act_bwd_apply_kernel<scalar_t, true>),
-            dim3(ew_grid(n, 256)), dim3(256), 0, s, pdy, px,
-            mean.data_ptr<float>(), rstd.data_ptr<float>(),
-            gm.data_ptr<float>(), bt.data_ptr<float>(),
-            s1.data_ptr<float>(), s2.data_ptr<float>(), ps, pdsk, pdx, n, C,
+  float* p1p = p1.data_ptr<float>();
+  float* p2p = p2.data_ptr<float>();
+  float* s1p = s1.data_ptr<float>();
+  float* s2p = s2.data_ptr<float>();
+  const BnParams p = bn_params(mean, rstd, gm, bt);
+  with_bool(has_skip, [&](auto hs) {
+    constexpr bool HS = decltype(hs)::value;
+    // reduce -> fixed-order finish -> apply, on one mapping
+    auto run = [&](auto tag, auto octet) {
+      using T = typename decltype(tag)::type;
+      constexpr bool OCT = decltype(octet)::value;
+      const T* pdy = ptr<const T>(dyc);
+      const T* px = ptr<const T>(xc);
+      const T* ps = ptr<const T>(sk);
+      if constexpr (OCT) {
+        // 2x unrolled (2-3 loads/iter already): 4-6 independent loads in
+        // flight (4x was measured SLOWER: 71 -> 98 us — register pressure)
+        launch_reduce8<2>(BnBwdRow8<HS>{pdy, px, ps, p, (int)act}, p1p, p2p,
+                          chunks, M, C, s);
+      } else {
+        launch_reduce(BnBwdElem<T, HS>{pdy, px, ps, p, (int)act}, p1p, p2p,
+                      chunks, M, C, s);
+      }
+      run_reduce_partials(p1p, p2p, s1p, s2p, chunks, C, s1.options(), s);
+      if constexpr (OCT) {
+        hipLaunchKernelGGL((bn_act_bwd_apply8_kernel<HS>),
+            dim3(1, rows8_blocks(M, C)), dim3(256), 0, s, pdy, px, p.mean,
+            p.rstd, p.gamma, p.beta, s1p, s2p, ps, ptr<T>(dsk), ptr<T>(dx),
+            M, C, (float)M, (int)act);
+      } else {
+        hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, HS>),
+            dim3(ew_grid(n, 256)), dim3(256), 0, s, pdy, px, p.mean, p.rstd,
+            p.gamma, p.beta, s1p, s2p, ps, ptr<T>(dsk), ptr<T>(dx), n, C,
             (float)M, (int)act);
-      else
-        hipLaunchKernelGGL((bn_act_bwd_apply_kernel<scalar_t, false>),
-            dim3(ew_grid(n, 256)), dim3(256), 0, s, pdy, px,
-            mean.data_ptr<float>(), rstd.data_ptr<float>(),
-            gm.data_ptr<float>(), bt.data_ptr<float>(),
-            s1.data_ptr<float>(), s2.data_ptr<float>(), ps, pdsk, pdx, n, C,
-            (float)M, (int)act);
-    });
-  }
+      }
+    };
+    if (fast8_ok(xc, C)) {
+      run(TypeTag<bf16>{}, std::true_type{});
+    } else {
+      with_dtype(xc, [&](auto tag) { run(tag, std::false_type{}); });
+    }
+  });
   HIP_CHECK_LAST();
   // dgamma = s2, dbeta = s1; dskip (= dpre) last when skip given
   if (has_skip) return {dx, s2, s1, dsk};

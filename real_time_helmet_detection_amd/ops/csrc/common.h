@@ -61,11 +61,12 @@ DEV_INLINE float apply_act(float x, int act) {
   return x;
 }
 
-// derivative of act as a function of the ACTIVATION OUTPUT y (valid for
-// monotone relu/lrelu/linear: sign(y) == sign(pre-act))
-DEV_INLINE float act_grad_from_out(float y, int act) {
-  if (act == ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (act == ACT_LRELU) return y > 0.f ? 1.f : 0.01f;
+// derivative of act from the SIGN of v, where v is the pre-activation or
+// the activation output (relu/lrelu/linear are monotone through 0, so
+// sign(output) == sign(pre-act) and either gives the same answer)
+DEV_INLINE float act_grad_by_sign(float v, int act) {
+  if (act == ACT_RELU) return v > 0.f ? 1.f : 0.f;
+  if (act == ACT_LRELU) return v > 0.f ? 1.f : 0.01f;
   return 1.f;
 }
 

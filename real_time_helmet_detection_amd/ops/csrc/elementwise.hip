@@ -46,12 +46,12 @@ __global__ void add_act_bwd_kernel(const T* __restrict__ dy,
       *reinterpret_cast<uint4*>(vy) = *reinterpret_cast<const uint4*>(y + i);
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
-        stf(&vdz[k], ldf(&vdy[k]) * act_grad_from_out(ldf(&vy[k]), act));
+        stf(&vdz[k], ldf(&vdy[k]) * act_grad_by_sign(ldf(&vy[k]), act));
       *reinterpret_cast<uint4*>(dz + i) = *reinterpret_cast<const uint4*>(vdz);
     }
   } else {
     for (; i < n; i += stride)
-      stf(&dz[i], ldf(&dy[i]) * act_grad_from_out(ldf(&y[i]), act));
+      stf(&dz[i], ldf(&dy[i]) * act_grad_by_sign(ldf(&y[i]), act));
   }
 }
 

@@ -6,6 +6,10 @@ relative-norm tolerances sized for bf16 accumulation; fp32 MFMA paths are
 exact-f32 (fmaf-chain numerics) and use tight tolerances.
 """
 
+import functools
+import math
+import types
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -713,6 +717,186 @@ def test_col_sum():
     want = x.sum(dim=(0, 2, 3))
     got = _C().col_sum(to_gpu(x))
     assert rel_err(got, want) < 1e-4
+
+
+# Direct tests of every bn.hip path. Oracles are float64 on the CPU, built
+# from the SAME rounded inputs the kernel reads (inputs are made in the
+# kernel's dtype first, then upcast), so a bf16 output differs from the
+# oracle by one bf16 rounding (2**-9 of the element) plus fp32 rounding
+# ahead of it: bound 2**-8. fp32 results keep the bounds used above.
+#
+# (shape, dtype): the smallest shapes that reach each path.
+BN_SHAPES = [
+    # octet path, chunks=10 -> two-stage finish; streams=32, 235 rows per
+    # chunk: unrolled trips plus a tail in both reduce kernels
+    ((2, 64, 25, 47), torch.bfloat16),
+    # octet path, chunks=1 -> single-kernel finish, streams=64
+    ((4, 32, 8, 8), torch.bfloat16),
+    # octs=256, streams=1: edge of the octet path, no tree steps
+    ((1, 2048, 3, 5), torch.bfloat16),
+    # octs=3 (not a power of two): scalar path in bf16
+    ((2, 24, 9, 11), torch.bfloat16),
+    # scalar path, partial channel tile with dead lanes
+    ((3, 33, 7, 9), torch.float32),
+    # scalar path with chunks=10
+    ((2, 64, 25, 47), torch.float32),
+]
+_BN_IDS = ['%s-%s' % ('x'.join(map(str, s)), str(d).split('.')[-1])
+           for s, d in BN_SHAPES]
+BN_BIG = BN_SHAPES[0]
+
+# Seeds picked on the CPU so that no pre-activation sits on the ReLU kink
+# (min|pre| > 1e-5, asserted in the test): a flipped sign there would
+# change dpre by the whole |dy|.
+_BN_SEEDS = {
+    # (shape, dtype, has_skip): seed             min|pre| on the oracle
+    ((2, 64, 25, 47), torch.bfloat16, False): 23,   # 3.3e-05
+    ((2, 64, 25, 47), torch.bfloat16, True): 20,    # 4.9e-05
+    ((4, 32, 8, 8), torch.bfloat16, False): 20,     # 3.7e-04
+    ((4, 32, 8, 8), torch.bfloat16, True): 20,      # 3.9e-04
+    ((1, 2048, 3, 5), torch.bfloat16, False): 20,   # 1.1e-04
+    ((1, 2048, 3, 5), torch.bfloat16, True): 20,    # 1.2e-04
+    ((2, 24, 9, 11), torch.bfloat16, False): 20,    # 2.3e-04
+    ((2, 24, 9, 11), torch.bfloat16, True): 20,     # 5.2e-04
+    ((3, 33, 7, 9), torch.float32, False): 20,      # 7.7e-04
+    ((3, 33, 7, 9), torch.float32, True): 20,       # 2.8e-05
+    ((2, 64, 25, 47), torch.float32, False): 36,    # 2.0e-05
+    ((2, 64, 25, 47), torch.float32, True): 23,     # 4.2e-05
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _bn_case(shape, dtype, has_skip):
+    """Seeded inputs (kernel dtype) and their float64 oracle; shared,
+    read-only."""
+    g = torch.Generator().manual_seed(_BN_SEEDS[(shape, dtype, has_skip)])
+    C = shape[1]
+
+    def rnd():
+        return (torch.randn(shape, generator=g) * 3 + 1).to(dtype)
+
+    c = types.SimpleNamespace(C=C, M=math.prod(shape) // C)
+    c.x, c.dy = rnd(), rnd()
+    c.skip = rnd() if has_skip else None
+    c.gamma = torch.rand(C, generator=g) + 0.5
+    c.beta = torch.rand(C, generator=g) - 0.5
+    x64 = c.x.double()
+    c.mean = x64.mean(dim=(0, 2, 3))
+    c.var = x64.var(dim=(0, 2, 3), unbiased=False)
+    c.rstd = (c.var + 1e-5).rsqrt()
+    # the kernels take fp32 statistics: the oracle uses the same rounded ones
+    c.mean32, c.rstd32 = c.mean.float(), c.rstd.float()
+
+    def ch(t):
+        return t.double().view(1, -1, 1, 1)
+
+    c.xh = (x64 - ch(c.mean32)) * ch(c.rstd32)
+    c.pre = c.xh * ch(c.gamma) + ch(c.beta)
+    if has_skip:
+        c.pre = c.pre + c.skip.double()
+    return c
+
+
+def _act64(pre, act):
+    return pre if act == 0 else (F.relu(pre) if act == 1
+                                 else F.leaky_relu(pre, 0.01))
+
+
+def _out_tol(dtype, f32_tol):
+    return 2.0 ** -8 if dtype == torch.bfloat16 else f32_tol
+
+
+@pytest.mark.parametrize('running', [False, True])
+@pytest.mark.parametrize('shape,dtype', BN_SHAPES, ids=_BN_IDS)
+def test_bn_stats_paths(shape, dtype, running):
+    c = _bn_case(shape, dtype, False)
+    g = torch.Generator().manual_seed(1)
+    rm0 = torch.randn(c.C, generator=g)
+    rv0 = torch.rand(c.C, generator=g) + 0.5
+    rm_g = rm0.cuda() if running else None
+    rv_g = rv0.cuda() if running else None
+    mean, rstd = _C().bn_stats(to_gpu(c.x, dtype), rm_g, rv_g, 0.1, 1e-5)
+    assert rel_err(mean, c.mean) < 1e-4
+    assert rel_err(rstd, c.rstd) < 1e-4
+    if running:
+        rm64, rv64 = rm0.double(), rv0.double()
+        F.batch_norm(c.x.double(), rm64, rv64, None, None, training=True,
+                     momentum=0.1, eps=1e-5)
+        assert rel_err(rm_g, rm64) < 1e-4
+        assert rel_err(rv_g, rv64) < 1e-4
+
+
+@pytest.mark.parametrize('has_skip', [False, True])
+@pytest.mark.parametrize('act', [0, 1, 2])
+@pytest.mark.parametrize('shape,dtype', BN_SHAPES, ids=_BN_IDS)
+def test_bn_act_fwd_paths(shape, dtype, act, has_skip):
+    c = _bn_case(shape, dtype, has_skip)
+    want = _act64(c.pre, act)
+    got = _C().bn_act_fwd(to_gpu(c.x, dtype), c.mean32.cuda(),
+                          c.rstd32.cuda(), c.gamma.cuda(), c.beta.cuda(),
+                          act, to_gpu(c.skip, dtype) if has_skip else None)
+    assert got.dtype == dtype and got.shape == c.x.shape
+    assert rel_err(got, want) < _out_tol(dtype, 1e-4)
+
+
+@pytest.mark.parametrize('has_skip', [False, True])
+@pytest.mark.parametrize('act', [0, 1, 2])
+@pytest.mark.parametrize('shape,dtype', BN_SHAPES, ids=_BN_IDS)
+def test_bn_act_bwd_paths(shape, dtype, act, has_skip):
+    c = _bn_case(shape, dtype, has_skip)
+    if act != 0:
+        # an assertion on the inputs, not a skip: the kernel's fp32 pre is
+        # within ~5e-7 of the oracle's, so no sign can differ
+        assert c.pre.abs().min().item() > 1e-5
+    slope = {0: 1.0, 1: 0.0, 2: 0.01}[act]
+    dpre = c.dy.double() * torch.where(c.pre > 0, 1.0, slope)
+    dbeta = dpre.sum(dim=(0, 2, 3))
+    dgamma = (dpre * c.xh).sum(dim=(0, 2, 3))
+
+    def ch(t):
+        return t.double().view(1, -1, 1, 1)
+
+    dx = ch(c.gamma) * ch(c.rstd32) * (dpre - ch(dbeta) / c.M
+                                       - c.xh * ch(dgamma) / c.M)
+    out = _C().bn_act_bwd(to_gpu(c.dy, dtype), to_gpu(c.x, dtype),
+                          c.mean32.cuda(), c.rstd32.cuda(), c.gamma.cuda(),
+                          c.beta.cuda(), act,
+                          to_gpu(c.skip, dtype) if has_skip else None)
+    assert len(out) == (4 if has_skip else 3)
+    assert out[0].dtype == dtype
+    assert rel_err(out[0], dx) < _out_tol(dtype, 1e-3)
+    assert rel_err(out[1], dgamma) < 1e-3
+    assert rel_err(out[2], dbeta) < 1e-3
+    if has_skip:
+        assert out[3].dtype == dtype
+        assert rel_err(out[3], dpre) < _out_tol(dtype, 1e-3)
+
+
+@pytest.mark.parametrize('shape,dtype', BN_SHAPES, ids=_BN_IDS)
+def test_col_sum_paths(shape, dtype):
+    c = _bn_case(shape, dtype, False)
+    got = _C().col_sum(to_gpu(c.x, dtype))
+    assert got.dtype == torch.float32
+    assert rel_err(got, c.x.double().sum(dim=(0, 2, 3))) < 1e-4
+
+
+def test_bn_deterministic():
+    """The fixed-order partial finish: identical inputs give BITWISE
+    identical statistics and gradients (two-stage finish, octet path)."""
+    shape, dtype = BN_BIG
+    c = _bn_case(shape, dtype, True)
+    x, dy, sk = (to_gpu(t, dtype) for t in (c.x, c.dy, c.skip))
+    runs = []
+    for _ in range(2):
+        rm = torch.zeros(c.C, device='cuda')
+        rv = torch.ones(c.C, device='cuda')
+        outs = list(_C().bn_stats(x, rm, rv, 0.1, 1e-5)) + [rm, rv]
+        outs += _C().bn_act_bwd(dy, x, c.mean32.cuda(), c.rstd32.cuda(),
+                                c.gamma.cuda(), c.beta.cuda(), 1, sk)
+        runs.append(outs)
+    assert len(runs[0]) == len(runs[1]) == 8
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize('cin', [6, 3, 20])
