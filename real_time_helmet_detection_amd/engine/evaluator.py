@@ -33,6 +33,38 @@ except ImportError:  # pragma: no cover
         return x
 
 
+def postprocess(p, boxes, clss, scores):
+    """Post-decode stage shared by Prediction and GraphedPredictor.
+
+    boxes (B,N,4), clss (B,N), scores (B,N) of the merged stacks -> per-image
+    lists (boxes, classes, scores). Both NMS modes run as one batched kernel
+    with the confidence filter folded in and ONE host sync (counts.cpu())
+    for the whole batch; 'soft-nms' returns the rescored scores.
+    """
+    b = boxes.shape[0]
+    box_lst, cls_lst, score_lst = [], [], []
+    if p.nms == 'nms':
+        idx, counts = ops.nms_batched(boxes, scores, p.nms_th, p.conf_th)
+        counts_l = counts.cpu().tolist()
+        for i in range(b):
+            sel = idx[i, :counts_l[i]].long()
+            box_lst.append(boxes[i][sel])
+            cls_lst.append(clss[i][sel])
+            score_lst.append(scores[i][sel])
+        return box_lst, cls_lst, score_lst
+    if p.nms == 'soft-nms':
+        idx, rescored, counts = ops.soft_nms_batched(
+            boxes, scores, 0.5, p.conf_th, p.conf_th)
+        counts_l = counts.cpu().tolist()
+        for i in range(b):
+            sel = idx[i, :counts_l[i]].long()
+            box_lst.append(boxes[i][sel])
+            cls_lst.append(clss[i][sel])
+            score_lst.append(rescored[i, :counts_l[i]])
+        return box_lst, cls_lst, score_lst
+    raise NotImplementedError('Not expected nms algorithm: %s' % p.nms)
+
+
 class Prediction(torch.nn.Module):
     """network forward -> sigmoid -> batched decode -> per-item NMS."""
 
@@ -70,29 +102,7 @@ class Prediction(torch.nn.Module):
         clss = clss.reshape(b, s * self.topk)
         scores = scores.reshape(b, s * self.topk)
 
-        box_lst, cls_lst, score_lst = [], [], []
-        if self.nms == 'nms':
-            # batched kernel with the confidence filter folded in: one
-            # launch + one host sync for the whole batch (the per-image
-            # loop paid a device sync per image)
-            idx, counts = ops.nms_batched(boxes, scores, self.nms_th,
-                                          self.conf_th)
-            counts_l = counts.cpu().tolist()
-            for i in range(b):
-                sel = idx[i, :counts_l[i]].long()
-                box_lst.append(boxes[i][sel])
-                cls_lst.append(clss[i][sel])
-                score_lst.append(scores[i][sel])
-            return box_lst, cls_lst, score_lst
-
-        for i in range(b):
-            keep = scores[i] >= self.conf_th
-            bi, ci, si = boxes[i][keep], clss[i][keep], scores[i][keep]
-            bi2, ci2, si2 = self.nonmaximum_supression(bi, ci, si)
-            box_lst.append(bi2)
-            cls_lst.append(ci2)
-            score_lst.append(si2)
-        return box_lst, cls_lst, score_lst
+        return postprocess(self, boxes, clss, scores)
 
     def nonmaximum_supression(self, boxes, clss, scores):
         if self.nms == 'nms':
@@ -269,23 +279,4 @@ class GraphedPredictor(torch.nn.Module):
         self.static_in.copy_(x)
         self.graph.replay()
         boxes, clss, scores = (t.clone() for t in self.static_out)
-        p = self.p
-        box_lst, cls_lst, score_lst = [], [], []
-        if p.nms == 'nms':
-            idx, counts = ops.nms_batched(boxes, scores, p.nms_th,
-                                          p.conf_th)
-            counts_l = counts.cpu().tolist()
-            for i in range(boxes.shape[0]):
-                sel = idx[i, :counts_l[i]].long()
-                box_lst.append(boxes[i][sel])
-                cls_lst.append(clss[i][sel])
-                score_lst.append(scores[i][sel])
-            return box_lst, cls_lst, score_lst
-        for i in range(boxes.shape[0]):
-            keep = scores[i] >= p.conf_th
-            bi, ci, si = boxes[i][keep], clss[i][keep], scores[i][keep]
-            bi, ci, si = p.nonmaximum_supression(bi, ci, si)
-            box_lst.append(bi)
-            cls_lst.append(ci)
-            score_lst.append(si)
-        return box_lst, cls_lst, score_lst
+        return postprocess(self.p, boxes, clss, scores)

@@ -8,6 +8,8 @@ python. ``export_model`` traces and saves the cpu/gpu variants
 (jit_traced_model_cpu.pth / jit_traced_model_gpu.pth, export.py:120-130).
 """
 
+from typing import Tuple
+
 import torch
 
 from ..ops import _backend
@@ -38,17 +40,60 @@ def nms_scripted(boxes: torch.Tensor, scores: torch.Tensor,
     return order[s > 0]
 
 
+@torch.jit.script
+def soft_nms_scripted(boxes: torch.Tensor, scores: torch.Tensor,
+                      sigma: float, score_th: float
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Gaussian soft-NMS with ops.eager.soft_nms semantics, scripted so the
+    data-dependent loop survives tracing. Returns (kept indices in
+    selection order, decayed scores at selection time)."""
+    n = boxes.shape[0]
+    b = boxes.float()
+    s = scores.float().clone()
+    area = (b[:, 2] - b[:, 0]).clamp(min=0.) * (b[:, 3] - b[:, 1]).clamp(min=0.)
+    # round 1 selects unconditionally; afterwards only scores > score_th live
+    alive = torch.ones(n, dtype=torch.bool, device=boxes.device)
+    keep = torch.zeros(n, dtype=torch.long, device=boxes.device)
+    kept = torch.zeros(n, dtype=torch.float32, device=boxes.device)
+    neg = torch.full_like(s, float('-inf'))
+    k = 0
+    while bool(alive.any()):
+        cur = torch.argmax(torch.where(alive, s, neg))
+        keep[k] = cur
+        kept[k] = s[cur]
+        k += 1
+        alive[cur] = False
+        xx1 = torch.max(b[cur, 0], b[:, 0])
+        yy1 = torch.max(b[cur, 1], b[:, 1])
+        xx2 = torch.min(b[cur, 2], b[:, 2])
+        yy2 = torch.min(b[cur, 3], b[:, 3])
+        inter = (xx2 - xx1).clamp(min=0.) * (yy2 - yy1).clamp(min=0.)
+        iou = inter / (area[cur] + area - inter).clamp(min=1e-9)
+        s = torch.where(alive, s * torch.exp(-(iou * iou) / sigma), s)
+        alive = alive & (s > score_th)
+    return keep[:k], kept[:k]
+
+
+NMS_MODES = ('nms', 'soft-nms')
+
+
 class Export(torch.nn.Module):
     """Traceable single-image predictor: net -> sigmoid -> decode -> NMS.
 
     Unlike the reference (which hardcoded split([2,2,2]) i.e. num_cls=2,
     export.py:31) the class count is taken from the constructor.
-    Returns (boxes, classes, scores) for the first batch item.
+    Returns (boxes, classes, scores) for the first batch item. ``nms``
+    selects 'nms' (greedy IoU) or 'soft-nms' (Gaussian, sigma 0.5, drop at
+    conf_th like ``Prediction``; returns the rescored scores).
     """
 
     def __init__(self, network, topk, scale_factor, conf_th, nms_th,
-                 normalized_coord=False, num_cls=2, pool_size=3):
+                 normalized_coord=False, num_cls=2, pool_size=3, nms='nms'):
         super().__init__()
+        if nms not in NMS_MODES:
+            raise NotImplementedError(
+                'Not expected nms algorithm: %s' % nms)
+        self.nms = nms
         self.network = network
         self.topk = topk
         self.scale_factor = scale_factor
@@ -84,6 +129,10 @@ class Export(torch.nn.Module):
         boxes = torch.cat(stack_boxes, dim=0)
         clss = torch.cat(stack_clss, dim=0)
         scores = torch.cat(stack_scores, dim=0)
+        if self.nms == 'soft-nms':
+            keep, rescored = soft_nms_scripted(boxes, scores, 0.5,
+                                               float(self.conf_th))
+            return boxes[keep], clss[keep], rescored
         keep = nms_scripted(boxes, scores, self.nms_th)
         return boxes[keep], clss[keep], scores[keep]
 
@@ -107,6 +156,10 @@ class Export(torch.nn.Module):
         scores = s.reshape(-1)
         keep = scores >= self.conf_th
         boxes, clss, scores = boxes[keep], clss[keep], scores[keep]
+        if self.nms == 'soft-nms':
+            keep, rescored = torch.ops.rthd.soft_nms(
+                boxes, scores, 0.5, float(self.conf_th))
+            return boxes[keep], clss[keep], rescored
         keep = torch.ops.rthd.nms(boxes, scores, float(self.nms_th))
         return boxes[keep], clss[keep], scores[keep]
 
@@ -116,7 +169,7 @@ def build_export_module(args, network):
         network=network, topk=args.topk, scale_factor=args.scale_factor,
         conf_th=args.conf_th, nms_th=args.nms_th,
         normalized_coord=args.normalized_coord, num_cls=args.num_cls,
-        pool_size=args.pool_size)
+        pool_size=args.pool_size, nms=args.nms)
 
 
 def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,

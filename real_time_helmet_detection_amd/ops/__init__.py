@@ -9,7 +9,9 @@ Every hot op of the detector goes through this module:
 
 Replaces, MI355X-natively, what the reference delegated to cuDNN/torchvision
 (SURVEY.md §2.3): fused conv+BN+act, pooling, upsample, the fused
-focal+L1 loss, the maxpool-peak top-k decode and NMS.
+focal+L1 loss, the maxpool-peak top-k decode, NMS and Gaussian soft-NMS
+(both NMS modes are batched kernels: one launch and one host sync per
+batch).
 """
 
 import torch
@@ -61,8 +63,19 @@ def nms_batched(boxes, scores, iou_threshold, conf_th):
 
 
 def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, score_th=0.001):
-    # O(N^2) sequential rescoring on <=few hundred boxes: host-side everywhere.
+    # serial argmax+decay rounds: one wave per image on GPU (soft_nms.hip);
+    # iou_threshold is unused by the Gaussian form on either side
+    if _hip(boxes):
+        from . import hip
+        return hip.soft_nms(boxes, scores, iou_threshold, sigma, score_th)
     return eager.soft_nms(boxes, scores, iou_threshold, sigma, score_th)
+
+
+def soft_nms_batched(boxes, scores, sigma, score_th, conf_th):
+    if _hip(boxes):
+        from . import hip
+        return hip.soft_nms_batched(boxes, scores, sigma, score_th, conf_th)
+    return eager.soft_nms_batched(boxes, scores, sigma, score_th, conf_th)
 
 
 def available():

@@ -46,6 +46,13 @@ std::vector<torch::Tensor> nms_batched(torch::Tensor boxes,
                                        torch::Tensor scores,
                                        double iou_threshold,
                                        double conf_th);
+std::vector<torch::Tensor> soft_nms_fwd(torch::Tensor boxes,
+                                        torch::Tensor scores, double sigma,
+                                        double score_th);
+std::vector<torch::Tensor> soft_nms_batched(torch::Tensor boxes,
+                                            torch::Tensor scores,
+                                            double sigma, double score_th,
+                                            double conf_th);
 
 torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16);
 torch::Tensor pack_weights_fp8(torch::Tensor w);
@@ -126,7 +133,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_fwd", &rthd::decode_fwd);
   m.def("nms_fwd", &rthd::nms_fwd);
   m.def("nms_batched", &rthd::nms_batched);
-  m.def("pack_weights", &rthd::pack_weights);
+  m.def("soft_nms", &rthd::soft_nms_fwd);
+  m.def("soft_nms_batched", &rthd::soft_nms_batched);
+  m.def("pack_weights",&rthd::pack_weights);
   m.def("pack_weights_fp8", &rthd::pack_weights_fp8);
   m.def("conv_fwd_fp8r", &rthd::conv_fwd_fp8r);
   m.def("conv_fwd", &rthd::conv_fwd);
@@ -175,6 +184,19 @@ static std::tuple<torch::Tensor, torch::Tensor> nms_batched_op(
   auto v = nms_batched(std::move(boxes), std::move(scores), iou, conf);
   return {v[0], v[1]};
 }
+static std::tuple<torch::Tensor, torch::Tensor> soft_nms_op(
+    torch::Tensor boxes, torch::Tensor scores, double sigma,
+    double score_th) {
+  auto v = soft_nms_fwd(std::move(boxes), std::move(scores), sigma, score_th);
+  return {v[0], v[1]};
+}
+static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+soft_nms_batched_op(torch::Tensor boxes, torch::Tensor scores, double sigma,
+                    double score_th, double conf) {
+  auto v = soft_nms_batched(std::move(boxes), std::move(scores), sigma,
+                            score_th, conf);
+  return {v[0], v[1], v[2]};
+}
 static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> decode_op(
     torch::Tensor hm, torch::Tensor off, torch::Tensor wh,
     int64_t scale_factor, int64_t topk, int64_t pool_size, bool normalized) {
@@ -200,6 +222,10 @@ TORCH_LIBRARY(rthd, m) {
   m.def("nms(Tensor boxes, Tensor scores, float iou) -> Tensor");
   m.def("nms_batched(Tensor boxes, Tensor scores, float iou, float conf) "
         "-> (Tensor, Tensor)");
+  m.def("soft_nms(Tensor boxes, Tensor scores, float sigma, "
+        "float score_th) -> (Tensor, Tensor)");
+  m.def("soft_nms_batched(Tensor boxes, Tensor scores, float sigma, "
+        "float score_th, float conf) -> (Tensor, Tensor, Tensor)");
   m.def("decode(Tensor hm, Tensor off, Tensor wh, int scale_factor, "
         "int topk, int pool_size, bool normalized) "
         "-> (Tensor, Tensor, Tensor)");
@@ -216,6 +242,8 @@ TORCH_LIBRARY_IMPL(rthd, CUDA, m) {
   m.impl("upsample2x_add", rthd::upsample2x_add_fwd);
   m.impl("nms", rthd::nms_fwd);
   m.impl("nms_batched", rthd::nms_batched_op);
+  m.impl("soft_nms", rthd::soft_nms_op);
+  m.impl("soft_nms_batched", rthd::soft_nms_batched_op);
   m.impl("decode", rthd::decode_op);
   m.impl("stem_im2col", rthd::stem_im2col);
 }

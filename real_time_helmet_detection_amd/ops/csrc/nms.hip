@@ -19,11 +19,9 @@
 
 #include <mutex>
 
-#include "common.h"
+#include "nms_common.h"
 
 namespace rthd {
-
-constexpr int NMS_CAP = 2048;
 
 // grid.x = image index (batched form; the single-image entry uses B=1).
 // conf: candidates with score < conf are neither suppressors nor output
@@ -106,20 +104,14 @@ __global__ void nms_kernel(const float* __restrict__ boxes,  // (B,N,4)
     const int i = t / W;
     const int w = t % W;
     const float ax1 = sx1[i], ay1 = sy1[i], ax2 = sx2[i], ay2 = sy2[i];
-    const float area_a = fmaxf(ax2 - ax1, 0.f) * fmaxf(ay2 - ay1, 0.f);
+    const float area_a = box_area(ax1, ay1, ax2, ay2);
     unsigned long long m = 0ull;
     const int j0 = w * 64;
     const int jend = min(j0 + 64, N);
     for (int j = max(j0, i + 1); j < jend; ++j) {
-      const float xx1 = fmaxf(ax1, sx1[j]);
-      const float yy1 = fmaxf(ay1, sy1[j]);
-      const float xx2 = fminf(ax2, sx2[j]);
-      const float yy2 = fminf(ay2, sy2[j]);
-      const float inter = fmaxf(xx2 - xx1, 0.f) * fmaxf(yy2 - yy1, 0.f);
-      const float area_b =
-          fmaxf(sx2[j] - sx1[j], 0.f) * fmaxf(sy2[j] - sy1[j], 0.f);
-      const float uni = area_a + area_b - inter;
-      if (inter / fmaxf(uni, 1e-9f) > thr) m |= 1ull << (j - j0);
+      const float iou = box_iou(ax1, ay1, ax2, ay2, area_a, sx1[j], sy1[j],
+                                sx2[j], sy2[j]);
+      if (iou > thr) m |= 1ull << (j - j0);
     }
     mask[(int64_t)i * W + w] = m;
   }

@@ -248,3 +248,25 @@ def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, score_th=0.001):
     device = boxes.device
     return (torch.tensor(keep, dtype=torch.long, device=device),
             torch.tensor(kept_scores, device=device))
+
+
+def soft_nms_batched(boxes, scores, sigma, score_th, conf_th):
+    """Eager twin of the batched soft-NMS kernel: per image, filter by
+    conf_th then Gaussian soft-NMS; returns (idx (B,N) int32 original
+    indices in selection order, rescored (B,N) float32 decayed scores at
+    selection time, counts (B) int32). Entries past counts[b] are 0."""
+    B, N = scores.shape
+    idx = torch.zeros(B, N, dtype=torch.int32, device=boxes.device)
+    out = torch.zeros(B, N, dtype=torch.float32, device=boxes.device)
+    counts = torch.zeros(B, dtype=torch.int32, device=boxes.device)
+    for i in range(B):
+        sel = (scores[i] >= conf_th).nonzero(as_tuple=False).squeeze(1)
+        if sel.numel() == 0:
+            continue
+        kept, rescored = soft_nms(boxes[i][sel], scores[i][sel],
+                                  sigma=sigma, score_th=score_th)
+        k = kept.numel()
+        counts[i] = k
+        idx[i, :k] = sel[kept].to(torch.int32)
+        out[i, :k] = rescored
+    return idx, out, counts

@@ -739,3 +739,27 @@ def nms(boxes, scores, iou_threshold):
         from .eager import nms as eager_nms
         return eager_nms(boxes, scores, iou_threshold)
     return _C().nms_fwd(boxes, scores, float(iou_threshold))
+
+
+def soft_nms_batched(boxes, scores, sigma, score_th, conf_th):
+    """Batched Gaussian soft-NMS with the confidence filter folded in: one
+    single-wave-per-image kernel and NO host sync (soft_nms.hip). boxes
+    (B,N,4), scores (B,N) -> (idx (B,N) int32, rescored (B,N) f32,
+    counts (B) int32), selection order, tails 0."""
+    if boxes.shape[1] > _NMS_CAP:
+        from .eager import soft_nms_batched as eager_snb
+        return eager_snb(boxes, scores, sigma, score_th, conf_th)
+    idx, rescored, counts = _C().soft_nms_batched(
+        boxes, scores, float(sigma), float(score_th), float(conf_th))
+    return idx, rescored, counts
+
+
+def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, score_th=0.001):
+    # iou_threshold is unused by Gaussian soft-NMS (kept for the eager
+    # signature)
+    if boxes.shape[0] > _NMS_CAP:
+        from .eager import soft_nms as eager_sn
+        return eager_sn(boxes, scores, iou_threshold, sigma, score_th)
+    keep, rescored = _C().soft_nms(boxes, scores, float(sigma),
+                                   float(score_th))
+    return keep, rescored

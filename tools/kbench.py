@@ -1,7 +1,8 @@
 """Micro-benchmark individual HIP kernels (A/B timing + rocprof target).
 
-python tools/kbench.py [wgrad|conv|stem_wgrad|bn|all] [--iters N]
-Prints per-kernel ms and effective TFLOP/s on the flagship shapes.
+python tools/kbench.py [wgrad|conv|stem_wgrad|bn|nms|all] [--iters N]
+Prints per-kernel ms and effective TFLOP/s on the flagship shapes; ``nms``
+prints the hard/soft batched NMS kernels against their eager twins.
 """
 import argparse
 import os
@@ -166,6 +167,64 @@ def bench_bn(iters):
     print(f'bn_act_bwd (all 3 kernels)    {ms*1e3:8.1f}us  {5*nbytes/ms/1e9:7.1f} GB/s')
 
 
+def clustered_boxes(b, n, seed):
+    """Seeded detector-like candidates: 8 cluster centres in a 512^2 frame,
+    centre + N(0,10), sides 40-80 px, scores U(0.05, 1)."""
+    g = torch.Generator().manual_seed(seed)
+    centres = torch.rand(b, 8, 2, generator=g) * 512
+    which = torch.randint(0, 8, (b, n), generator=g)
+    c = torch.gather(centres, 1, which[..., None].expand(b, n, 2)) \
+        + torch.randn(b, n, 2, generator=g) * 10
+    wh = 40 + 40 * torch.rand(b, n, 2, generator=g)
+    boxes = torch.cat([c - wh / 2, c + wh / 2], dim=2)
+    scores = 0.05 + 0.95 * torch.rand(b, n, generator=g)
+    return boxes.cuda(), scores.cuda()
+
+
+def wall_ms(fn, iters, warmup=2):
+    """Wall clock per call; fn ends with the host sync its caller pays."""
+    import time
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / iters
+
+
+def bench_nms(iters):
+    """Hard and soft batched NMS incl. the counts.cpu() sync, HIP kernel vs
+    the eager twin on the same GPU tensors (what RTHD_EAGER_GPU=1 runs)."""
+    from real_time_helmet_detection_amd.ops import eager, hip
+    conf = 0.3
+    print('batched NMS + counts.cpu(), conf_th %.1f, wall us per call' % conf)
+    print('%-5s %2s %4s %5s %10s %10s %8s'
+          % ('mode', 'B', 'N', 'kept', 'kernel', 'eager', 'ratio'))
+    for b in (1, 8):
+        for n in (100, 400):
+            boxes, scores = clustered_boxes(b, n, seed=b * 1000 + n)
+            runs = (
+                ('hard',
+                 lambda: hip.nms_batched(boxes, scores, 0.5, conf)[-1].cpu(),
+                 lambda: eager.nms_batched(boxes, scores, 0.5,
+                                           conf)[-1].cpu()),
+                ('soft',
+                 lambda: hip.soft_nms_batched(boxes, scores, 0.5, conf,
+                                              conf)[-1].cpu(),
+                 lambda: eager.soft_nms_batched(boxes, scores, 0.5, conf,
+                                                conf)[-1].cpu()),
+            )
+            for mode, kern, eag in runs:
+                kept = int(kern().sum())
+                k_ms = wall_ms(kern, iters)
+                e_ms = wall_ms(eag, max(2, iters // 10), warmup=1)
+                print('%-5s %2d %4d %5d %10.1f %10.1f %7.1fx'
+                      % (mode, b, n, kept, k_ms * 1e3, e_ms * 1e3,
+                         e_ms / k_ms))
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('which', nargs='?', default='all')
@@ -182,3 +241,5 @@ if __name__ == '__main__':
         bench_stem(args.iters)
     if args.which in ('bn', 'all'):
         bench_bn(args.iters)
+    if args.which in ('nms', 'all'):
+        bench_nms(args.iters)
