@@ -55,6 +55,9 @@ std::vector<torch::Tensor> soft_nms_batched(torch::Tensor boxes,
                                             double conf_th);
 
 torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16);
+std::vector<torch::Tensor> pack_weights_pair(torch::Tensor w,
+                                             bool to_bf16_fwd,
+                                             bool to_bf16_dgrad);
 torch::Tensor pack_weights_fp8(torch::Tensor w);
 torch::Tensor conv_fwd_fp8r(torch::Tensor x, torch::Tensor wpk,
                             torch::Tensor scale, torch::Tensor shift,
@@ -136,6 +139,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("soft_nms", &rthd::soft_nms_fwd);
   m.def("soft_nms_batched", &rthd::soft_nms_batched);
   m.def("pack_weights",&rthd::pack_weights);
+  m.def("pack_weights_pair", &rthd::pack_weights_pair);
   m.def("pack_weights_fp8", &rthd::pack_weights_fp8);
   m.def("conv_fwd_fp8r", &rthd::conv_fwd_fp8r);
   m.def("conv_fwd", &rthd::conv_fwd);

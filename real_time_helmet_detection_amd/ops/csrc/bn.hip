@@ -9,8 +9,10 @@
 //
 // Reduction design (the first version used per-channel atomicAdd from every
 // block: ~2k same-address atomic RMWs serialize to ~250 us per call):
-// blocks write per-chunk PARTIALS with plain stores; a tiny second kernel
-// sums the [chunks][C] partials — contention-free AND deterministic.
+// blocks write per-chunk PARTIALS; the last blocks to arrive sum the
+// [chunks][C] partials in a fixed order, in the same launch ("ticket" path;
+// RTHD_BN_STAGED=1 selects the older finish by two further tiny launches) —
+// contention-free AND deterministic.
 //
 // bf16 kernels use the row-interleaved octet mapping: thread t owns channel
 // octet t%octs across rows t/octs + k*streams, so a wave reads contiguous
@@ -23,7 +25,11 @@
 // the skeleton as its first argument.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <map>
+#include <mutex>
 #include <type_traits>
+#include <utility>
+#include <vector>
 #include "common.h"
 
 namespace rthd {
@@ -97,7 +103,10 @@ static int pick_chunks(int64_t M, int C) {
 // ----------------------------- reduce functors ------------------------------
 // Reduce functors add one element (scalar) or one octet row into two
 // accumulators; kTwo == false means the second sum does not exist (no LDS,
-// no work, no store).
+// no work, no store). kTailRows (octet functors): how many partial rows per
+// thread the ticket tail loads ahead of its adds — as many as fit in the
+// registers the functor's streaming loop already takes, and no more, so the
+// tail never costs the loop a wave of occupancy.
 
 template <typename T, bool WANT_SQ>
 struct ColSumElem {
@@ -115,6 +124,7 @@ struct ColSumElem {
 template <bool WANT_SQ>
 struct ColSumRow8 {
   static constexpr bool kTwo = WANT_SQ;
+  static constexpr int kTailRows = WANT_SQ ? 7 : 8;
   const bf16* x;
   struct Ch {};
   struct Row {
@@ -158,6 +168,7 @@ struct BnBwdElem {
 template <bool HAS_SKIP>
 struct BnBwdRow8 {
   static constexpr bool kTwo = true;
+  static constexpr int kTailRows = 16;
   const bf16 *dy, *x, *skip;
   BnParams p;
   int act;
@@ -184,15 +195,245 @@ struct BnBwdRow8 {
   }
 };
 
+// ------------- deterministic finish of [chunks][C] partials, in-kernel -------
+// The partial rows are summed in ONE fixed order whichever path runs:
+//   chunks <= 8: out[c] = p[0][c] + p[1][c] + ...             (sequential)
+//   chunks  > 8: 8 K-slices [K*s/8, K*(s+1)/8); per slice four sub-streams
+//                k0+sub, +4, ... then sum4 -> stage[s][c]; out[c] = the
+//                sequential sum of the 8 stage rows.
+// The staged path does this with reduce_partials_kernel + reduce_final_kernel
+// behind the reduce launch. The ticket path does it in the reduce launch's
+// own tail: a block publishes its partial row and draws a ticket on its
+// slice's counter; the block that draws the slice's last ticket reduces the
+// slice and draws a ticket on the top counter; the last of those runs the
+// final sum (and the BN finalize). Same reads, same adds, same order — the
+// two paths are bitwise identical, and two dependent launches shorter.
+
+// mean/rstd + running-stat update fused behind the final sum (mean != null)
+struct BnFinalize {
+  float* mean = nullptr;
+  float* rstd = nullptr;
+  float* run_mean = nullptr;
+  float* run_var = nullptr;
+  float Mf = 1.f, momentum = 0.1f, eps = 1e-5f;
+};
+
+// what the tail of a reduce launch needs; cnt == nullptr: no tail, the
+// launch only writes partials (staged path)
+struct BnTicket {
+  int* cnt = nullptr;  // kTicketCounters lines of 128 B per blockIdx.x
+  float *st1 = nullptr, *st2 = nullptr;  // [8][C] stage rows (chunks > 8)
+  float *o1 = nullptr, *o2 = nullptr;    // [C] sums
+  BnFinalize fin;
+};
+
+constexpr int kTicketSlices = 8;
+constexpr int kTicketCounters = kTicketSlices + 1;  // 8 slices + top level
+
+// out[c] = sequential sum of K rows of s1 (and s2), then the optional
+// finalize: the whole per-channel work of the last stage. Up to 8 rows (all
+// but the widest staged reduce) are loaded before the first add, so the
+// block pays one memory round trip and not K dependent ones; the adds keep
+// their order.
+template <bool TWO>
+DEV_INLINE void reduce_final_channel(const float* s1, const float* s2,
+                                     float* o1, float* o2, int K, int C,
+                                     int c, const BnFinalize& fin) {
+  float a = 0.f, b = 0.f;
+  if (K <= 8) {
+    float va[8], vb[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      // always a valid row; 32-bit: the kernels' C is far below 2^28
+      const unsigned i = (unsigned)min(k, K - 1) * (unsigned)C + c;
+      va[k] = s1[i];
+      if (TWO) vb[k] = s2[i];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      if (k < K) {
+        a += va[k];
+        if (TWO) b += vb[k];
+      }
+    }
+  } else {
+    for (int k = 0; k < K; ++k) a += s1[(int64_t)k * C + c];
+    if (TWO) {
+      for (int k = 0; k < K; ++k) b += s2[(int64_t)k * C + c];
+    }
+  }
+  o1[c] = a;
+  if (TWO) o2[c] = b;
+  if (fin.mean) {
+    const float mu = a / fin.Mf;
+    float var = b / fin.Mf - mu * mu;
+    var = fmaxf(var, 0.f);
+    fin.mean[c] = mu;
+    fin.rstd[c] = rsqrtf(var + fin.eps);
+    if (fin.run_mean) {
+      fin.run_mean[c] =
+          (1.f - fin.momentum) * fin.run_mean[c] + fin.momentum * mu;
+      const float ub = fin.Mf > 1.f ? var * fin.Mf / (fin.Mf - 1.f) : var;
+      fin.run_var[c] =
+          (1.f - fin.momentum) * fin.run_var[c] + fin.momentum * ub;
+    }
+  }
+}
+
+// A store another block of the same launch will read: write-through (sc1), so
+// it needs no release fence behind it. A release fence writes the XCD's L2
+// back once per block, and those serialise: the 1024-block stats reduce took
+// 49 us with plain stores + a lane-0 release fence per block, 12 us with no
+// tail at all (profiles/train_step_profile.md, "Single-launch BN reductions").
+DEV_INLINE void st_publish(float* p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Draws a ticket on *cnt once everything this block has st_publish-ed is
+// out. True (in every thread) in the block that drew the last of n tickets;
+// that block has acquired what the n-1 others published, and has put the
+// counter back to zero for the next launch on the stream. Every storing
+// wave drains its own stores ahead of the barrier; the ticket and the one
+// acquire are lane 0's alone.
+DEV_INLINE bool ticket_is_last(int* cnt, int n, int* flag) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = t == n - 1;
+    if (last) {
+      __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    *flag = last ? 1 : 0;
+  }
+  __syncthreads();
+  return *flag != 0;
+}
+
+// stage row of one K-slice for channels [c_lo, c_hi), 64 * V at a time:
+// thread = (V adjacent channels, sub-stream); each accumulator sums exactly
+// what its thread of reduce_partials_kernel sums, in that order. A slice of
+// the flagship's 128 chunks is 64 KB per sum, read by this one block, which
+// every other block of the launch is waiting for: U rows per thread are
+// loaded (8 B per lane with V = 2) before the first add.
+template <int V>
+DEV_INLINE void ld_rowv(float (&v)[V], const float* p, unsigned off) {
+  if constexpr (V == 2) {
+    const float2 t = *reinterpret_cast<const float2*>(p + off);
+    v[0] = t.x;
+    v[1] = t.y;
+  } else {
+    v[0] = p[off];
+  }
+}
+
+template <bool TWO, int U, int V>
+DEV_INLINE void ticket_reduce_slice(const float* p1, const float* p2,
+                                    float* o1, float* o2, int k0, int k1,
+                                    int c_lo, int c_hi, int C, float* sh) {
+  // 32-bit element offsets (chunks * C <= 1024 * 2048) on the uniform row
+  // bases: one offset register serves both sums
+  const int sub = threadIdx.x >> 6;
+  for (int cb = c_lo; cb < c_hi; cb += 64 * V) {
+    const int c = cb + (threadIdx.x & 63) * V;
+    float a[V] = {}, b[V] = {};
+    if (c < c_hi) {
+      // every round loads U rows before its first add, the last one too:
+      // a row past the slice is loaded from row k instead and not added
+      for (int k = k0 + sub; k < k1; k += 4 * U) {
+        float va[U][V], vb[U][V];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int kk = k + 4 * u < k1 ? k + 4 * u : k;
+          const unsigned off = (unsigned)kk * (unsigned)C + c;
+          ld_rowv<V>(va[u], p1, off);
+          if (TWO) ld_rowv<V>(vb[u], p2, off);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (k + 4 * u < k1) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+              a[v] += va[u][v];
+              if (TWO) b[v] += vb[u][v];
+            }
+          }
+        }
+      }
+    }
+    // sum4 tiles: [sum][v][256]
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      sh[v * 256 + threadIdx.x] = a[v];
+      if (TWO) sh[(V + v) * 256 + threadIdx.x] = b[v];
+    }
+    __syncthreads();
+    if (sub == 0 && c < c_hi) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        st_publish(&o1[c + v], sum4(sh + v * 256));
+        if (TWO) st_publish(&o2[c + v], sum4(sh + (V + v) * 256));
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Tail of a reduce launch, entered by every thread of every block after the
+// block's partial row is stored. The block owns channels [c_lo, c_hi) of
+// grid column blockIdx.x; sh is >= kTicketLds floats of the block's LDS
+// that nobody reads any more.
+// V = 2 needs c_lo, c_hi and C to be multiples of 128 and four sum4 tiles.
+constexpr int kTicketLds = 2 * 256 + 1;  // two sum4 tiles + the "last" flag
+constexpr int kTicketLdsWide = 4 * 256 + 1;
+// counters sit one to a 128-B line: the tickets of a 1024-block launch on
+// nine adjacent words serialise on that one line (about 17 ns each)
+constexpr int kTicketStride = 32;
+
+template <bool TWO, int U, bool WIDE>
+DEV_INLINE void ticket_finish(const BnTicket& t, const float* p1,
+                              const float* p2, int c_lo, int c_hi, int C,
+                              float* sh) {
+  const int K = gridDim.y;
+  int* cnt = t.cnt + blockIdx.x * (kTicketCounters * kTicketStride);
+  int* flag = reinterpret_cast<int*>(sh + (WIDE ? 4 : 2) * 256);
+  const float *f1 = p1, *f2 = p2;
+  int fk = K;
+  if (K > kTicketSlices) {
+    int s = 0;  // the slice with k0 <= blockIdx.y < k1
+    while ((K * (s + 1)) / kTicketSlices <= (int)blockIdx.y) ++s;
+    const int k0 = (K * s) / kTicketSlices;
+    const int k1 = (K * (s + 1)) / kTicketSlices;
+    if (!ticket_is_last(cnt + s * kTicketStride, k1 - k0, flag)) return;
+    float* o1 = t.st1 + (int64_t)s * C;
+    float* o2 = t.st2 + (int64_t)s * C;
+    if (WIDE && C % 128 == 0)
+      ticket_reduce_slice<TWO, U, 2>(p1, p2, o1, o2, k0, k1, c_lo, c_hi, C,
+                                     sh);
+    else
+      ticket_reduce_slice<TWO, U, 1>(p1, p2, o1, o2, k0, k1, c_lo, c_hi, C,
+                                     sh);
+    f1 = t.st1;
+    f2 = t.st2;
+    fk = kTicketSlices;
+  }
+  if (!ticket_is_last(cnt + kTicketSlices * kTicketStride, fk, flag)) return;
+  for (int c = c_lo + threadIdx.x; c < c_hi; c += 256)
+    reduce_final_channel<TWO>(f1, f2, t.o1, t.o2, fk, C, c, t.fin);
+}
+
 // --------------------------- reduce skeletons -------------------------------
 // Both: grid.y = row chunks; block y reduces rows [r0, r1) of every channel
-// it owns and stores one partial row p1[y][C] (and p2[y][C]).
+// it owns and stores one partial row p1[y][C] (and p2[y][C]); with a ticket
+// the launch also finishes the reduction (above).
 
 // scalar, any C: block = 64 channels x 4 row sub-streams, grid (C/64, chunks)
 template <typename F>
-__global__ void reduce_part_kernel(const F f, float* __restrict__ p1,
-                                   float* __restrict__ p2, int64_t M,
-                                   int C) {
+__global__ void reduce_part_kernel(const F f, float* p1, float* p2,
+                                   int64_t M, int C, const BnTicket tk) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int sub = threadIdx.x >> 6;
   const bool live = c < C;
@@ -204,23 +445,28 @@ __global__ void reduce_part_kernel(const F f, float* __restrict__ p1,
     const typename F::Ch ch = f.channel(c);
     for (int64_t r = r0 + sub; r < r1; r += 4) f.add(ch, r * C + c, a1, a2);
   }
-  __shared__ float sh1[256], sh2[F::kTwo ? 256 : 1];
+  // one LDS object: the two sum4 tiles, and the ticket tail's flag word
+  __shared__ float sh[kTicketLds];
+  float* sh1 = sh;
+  float* sh2 = sh + 256;
   sh1[threadIdx.x] = a1;
   if (F::kTwo) sh2[threadIdx.x] = a2;
   __syncthreads();
   if (sub == 0 && live) {
-    p1[(int64_t)blockIdx.y * C + c] = sum4(sh1);
-    if (F::kTwo) p2[(int64_t)blockIdx.y * C + c] = sum4(sh2);
+    st_publish(&p1[(int64_t)blockIdx.y * C + c], sum4(sh1));
+    if (F::kTwo) st_publish(&p2[(int64_t)blockIdx.y * C + c], sum4(sh2));
   }
+  if (tk.cnt)
+    ticket_finish<F::kTwo, 8, false>(tk, p1, p2, blockIdx.x * 64,
+                           min(C, (int)blockIdx.x * 64 + 64), C, sh);
 }
 
 // bf16 octets, C = 8*2^k: block = octs x streams threads, grid (1, chunks),
 // LDS halving tree over the streams. UNROLL rows are loaded before any is
 // consumed (independent 16-B loads in flight).
 template <int UNROLL, typename F>
-__global__ void reduce8_part_kernel(const F f, float* __restrict__ p1,
-                                    float* __restrict__ p2, int64_t M,
-                                    int C) {
+__global__ void reduce8_part_kernel(const F f, float* p1, float* p2,
+                                    int64_t M, int C, const BnTicket tk) {
   const int octs = C >> 3;
   const int streams = blockDim.x / octs;
   const int oct = threadIdx.x % octs;
@@ -267,10 +513,18 @@ __global__ void reduce8_part_kernel(const F f, float* __restrict__ p1,
   if (rs == 0) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      p1[(int64_t)blockIdx.y * C + c0 + e] = sh1[threadIdx.x][e];
-      if (F::kTwo) p2[(int64_t)blockIdx.y * C + c0 + e] = sh2[threadIdx.x][e];
+      st_publish(&p1[(int64_t)blockIdx.y * C + c0 + e], sh1[threadIdx.x][e]);
+      if (F::kTwo)
+        st_publish(&p2[(int64_t)blockIdx.y * C + c0 + e],
+                   sh2[threadIdx.x][e]);
     }
   }
+  // the tail borrows sh1 (2048 floats >= kTicketLdsWide): no further LDS
+  // object
+  static_assert(sizeof(sh1) >= kTicketLdsWide * sizeof(float), "tail LDS");
+  if (tk.cnt)
+    ticket_finish<F::kTwo, F::kTailRows, true>(tk, p1, p2, 0, C, C,
+                                               &sh1[0][0]);
 }
 
 // ------------------------------ apply kernels -------------------------------
@@ -402,7 +656,7 @@ __global__ void bn_act_bwd_apply8_kernel(
   }
 }
 
-// ------------------ deterministic finish of [chunks][C] partials ------------
+// ------------- staged finish of [chunks][C] partials: two launches -----------
 
 // stage1[ks][c] = sum of the ks-th K-slice of p[k][c] (and stage2/p2).
 // block = 64 channels x 4 k-substreams (a K=256 serial loop in one tiny
@@ -450,37 +704,19 @@ __global__ void reduce_final_kernel(const float* __restrict__ s1,
                                     float eps = 1e-5f) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  float a = 0.f;
-  for (int k = 0; k < K; ++k) a += s1[(int64_t)k * C + c];
-  o1[c] = a;
-  float b = 0.f;
-  if (o2) {
-    for (int k = 0; k < K; ++k) b += s2[(int64_t)k * C + c];
-    o2[c] = b;
-  }
-  if (fin_mean) {
-    const float mu = a / Mf;
-    float var = b / Mf - mu * mu;
-    var = fmaxf(var, 0.f);
-    fin_mean[c] = mu;
-    fin_rstd[c] = rsqrtf(var + eps);
-    if (run_mean) {
-      run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mu;
-      const float ub = Mf > 1.f ? var * Mf / (Mf - 1.f) : var;
-      run_var[c] = (1.f - momentum) * run_var[c] + momentum * ub;
-    }
-  }
+  BnFinalize fin;
+  fin.mean = fin_mean;
+  fin.rstd = fin_rstd;
+  fin.run_mean = run_mean;
+  fin.run_var = run_var;
+  fin.Mf = Mf;
+  fin.momentum = momentum;
+  fin.eps = eps;
+  if (o2) reduce_final_channel<true>(s1, s2, o1, o2, K, C, c, fin);
+  else reduce_final_channel<false>(s1, s2, o1, o2, K, C, c, fin);
 }
 
 // --------------------------------- host -------------------------------------
-
-struct BnFinalize {
-  float* mean = nullptr;
-  float* rstd = nullptr;
-  float* run_mean = nullptr;
-  float* run_var = nullptr;
-  float Mf = 1.f, momentum = 0.1f, eps = 1e-5f;
-};
 
 static BnFinalize make_finalize(torch::Tensor& mean, torch::Tensor& rstd,
                                 c10::optional<torch::Tensor>& running_mean,
@@ -532,6 +768,95 @@ static void run_reduce_partials(const float* p1, const float* p2,
   finish(s1, s2, ks);
 }
 
+// ---- ticket counters: one zeroed int32 page per (device, stream) ----------
+// Every counter is put back to zero by the block that draws its last ticket,
+// so consecutive launches on a stream share one page with no memset node
+// between them; launches on different streams may overlap and get different
+// pages. Pages are cut from a per-device pool that is allocated and zeroed
+// on the first eager (non-capturing) call; handing a page of an existing
+// pool to a new stream touches no memory, so it is legal during stream
+// capture — a hipGraph captured after an eager warm-up gets the ticket path
+// on its own capture stream. With no pool yet (or none left) during a
+// capture, that call takes the staged path. The kernels of one captured
+// graph share the capture stream's page: replays of graphs captured on the
+// same stream must not overlap each other (they never do here: one stream
+// replays them in order).
+
+// >= kTicketCounters * kTicketStride * grid.x: 14 grid columns, C <= 896 on
+// the scalar skeleton (wider ones stay staged)
+constexpr int kTicketPageInts = 4096;
+constexpr int kTicketPoolPages = 32;
+
+static bool bn_stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    return true;  // be conservative: allocate nothing
+  }
+  return st != hipStreamCaptureStatusNone;
+}
+
+// nullptr: take the staged path
+static int* ticket_counters(const torch::Tensor& like, hipStream_t s,
+                            int grid_x) {
+  const char* e = getenv("RTHD_BN_STAGED");
+  if (e && e[0] == '1' && e[1] == '\0') return nullptr;
+  if ((int64_t)grid_x * kTicketCounters * kTicketStride > kTicketPageInts)
+    return nullptr;
+  struct Pool {
+    std::vector<torch::Tensor> slabs;
+    int used = 0;  // pages handed out of slabs.back()
+  };
+  static std::mutex mu;
+  static std::map<int, Pool> pools;
+  static std::map<std::pair<int, hipStream_t>, int*> pages;
+  const int dev = like.device().index();
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = pages.find({dev, s});
+  if (it != pages.end()) return it->second;
+  Pool& pool = pools[dev];
+  if (pool.slabs.empty() || pool.used == kTicketPoolPages) {
+    if (bn_stream_capturing(s)) return nullptr;
+    pool.slabs.push_back(torch::zeros(
+        {(int64_t)kTicketPoolPages * kTicketPageInts},
+        like.options().dtype(at::kInt)));
+    pool.used = 0;
+    // the zero fill ran on s; any other stream may be handed a page later
+    if (hipStreamSynchronize(s) != hipSuccess) {
+      (void)hipGetLastError();
+      pool.slabs.pop_back();
+      pool.used = kTicketPoolPages;
+      return nullptr;
+    }
+  }
+  int* page = pool.slabs.back().data_ptr<int>() +
+              (int64_t)pool.used++ * kTicketPageInts;
+  pages.emplace(std::make_pair(dev, s), page);
+  return page;
+}
+
+// The finish of one reduce launch: a ticket for the launch to finish itself
+// (tk.cnt set), or, staged, the two finish launches behind it.
+struct BnFinish {
+  BnTicket tk;
+  torch::Tensor stage;  // keeps tk.st1/st2 alive
+
+  BnFinish(const torch::Tensor& like, int grid_x, int chunks, int C,
+           float* o1, float* o2, const torch::TensorOptions& opt,
+           hipStream_t s, const BnFinalize& fin = BnFinalize{}) {
+    tk.cnt = ticket_counters(like, s, grid_x);
+    if (!tk.cnt) return;
+    if (chunks > kTicketSlices) {
+      stage = torch::empty({(int64_t)2 * kTicketSlices * C}, opt);
+      tk.st1 = stage.data_ptr<float>();
+      tk.st2 = tk.st1 + (int64_t)kTicketSlices * C;
+    }
+    tk.o1 = o1;
+    tk.o2 = o2;
+    tk.fin = fin;
+  }
+};
+
 // runtime bool / dtype -> compile-time argument of a generic lambda
 template <typename Fn>
 static void with_bool(bool b, Fn&& fn) {
@@ -569,16 +894,18 @@ static BnParams bn_params(const torch::Tensor& mean, const torch::Tensor& rstd,
 // one launch site per reduce skeleton
 template <typename F>
 static void launch_reduce(const F& f, float* p1, float* p2, int chunks,
-                          int64_t M, int C, hipStream_t s) {
+                          int64_t M, int C, hipStream_t s,
+                          const BnTicket& tk) {
   hipLaunchKernelGGL((reduce_part_kernel<F>), dim3(cdiv(C, 64), chunks),
-      dim3(256), 0, s, f, p1, p2, M, C);
+      dim3(256), 0, s, f, p1, p2, M, C, tk);
 }
 
 template <int UNROLL, typename F>
 static void launch_reduce8(const F& f, float* p1, float* p2, int chunks,
-                           int64_t M, int C, hipStream_t s) {
+                           int64_t M, int C, hipStream_t s,
+                           const BnTicket& tk) {
   hipLaunchKernelGGL((reduce8_part_kernel<UNROLL, F>), dim3(1, chunks),
-      dim3(256), 0, s, f, p1, p2, M, C);
+      dim3(256), 0, s, f, p1, p2, M, C, tk);
 }
 
 // grid of the octet apply kernels: (1, nb) blocks of 256
@@ -596,7 +923,11 @@ static void run_colsum(const torch::Tensor& xc, torch::Tensor& sum,
   if (sumsq) p2 = torch::empty({chunks, C}, sum.options());
   float* p1p = p1.data_ptr<float>();
   float* p2p = ptr<float>(p2);
+  float* o1p = sum.data_ptr<float>();
+  float* o2p = sumsq ? sumsq->data_ptr<float>() : nullptr;
   const bool fast8 = fast8_ok(xc, C);
+  const BnFinish done(xc, fast8 ? 1 : (int)cdiv(C, 64), chunks, C, o1p, o2p,
+                      sum.options(), s, fin);
   with_bool(sumsq != nullptr, [&](auto want_sq) {
     constexpr bool SQ = decltype(want_sq)::value;
     if (fast8) {
@@ -604,18 +935,18 @@ static void run_colsum(const torch::Tensor& xc, torch::Tensor& sum,
       // flight across the chip (< the ~6 MB needed to cover HBM latency at
       // 8 TB/s); four independent loads per iteration saturate the bus.
       launch_reduce8<4>(ColSumRow8<SQ>{ptr<const bf16>(xc)}, p1p, p2p,
-                        chunks, M, C, s);
+                        chunks, M, C, s, done.tk);
     } else {
       with_dtype(xc, [&](auto tag) {
         using T = typename decltype(tag)::type;
         launch_reduce(ColSumElem<T, SQ>{ptr<const T>(xc)}, p1p, p2p, chunks,
-                      M, C, s);
+                      M, C, s, done.tk);
       });
     }
   });
-  run_reduce_partials(p1p, p2p, sum.data_ptr<float>(),
-                      sumsq ? sumsq->data_ptr<float>() : nullptr, chunks,
-                      C, sum.options(), s, fin);
+  if (!done.tk.cnt)
+    run_reduce_partials(p1p, p2p, o1p, o2p, chunks, C, sum.options(), s,
+                        fin);
 }
 
 std::vector<torch::Tensor> bn_stats(torch::Tensor x,
@@ -625,7 +956,7 @@ std::vector<torch::Tensor> bn_stats(torch::Tensor x,
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   const int C = xc.size(1);
   const int64_t M = xc.numel() / C;
-  // fully overwritten by reduce_final_kernel (no zero-init kernels)
+  // fully overwritten by the final sum (no zero-init kernels)
   auto sum = torch::empty({C}, xc.options().dtype(at::kFloat));
   auto sumsq = torch::empty({C}, xc.options().dtype(at::kFloat));
   auto mean = torch::empty({C}, xc.options().dtype(at::kFloat));
@@ -733,6 +1064,9 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
   float* s1p = s1.data_ptr<float>();
   float* s2p = s2.data_ptr<float>();
   const BnParams p = bn_params(mean, rstd, gm, bt);
+  const bool fast8 = fast8_ok(xc, C);
+  const BnFinish done(xc, fast8 ? 1 : (int)cdiv(C, 64), chunks, C, s1p, s2p,
+                      s1.options(), s);
   with_bool(has_skip, [&](auto hs) {
     constexpr bool HS = decltype(hs)::value;
     // reduce -> fixed-order finish -> apply, on one mapping
@@ -746,12 +1080,13 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
         // 2x unrolled (2-3 loads/iter already): 4-6 independent loads in
         // flight (4x was measured SLOWER: 71 -> 98 us — register pressure)
         launch_reduce8<2>(BnBwdRow8<HS>{pdy, px, ps, p, (int)act}, p1p, p2p,
-                          chunks, M, C, s);
+                          chunks, M, C, s, done.tk);
       } else {
         launch_reduce(BnBwdElem<T, HS>{pdy, px, ps, p, (int)act}, p1p, p2p,
-                      chunks, M, C, s);
+                      chunks, M, C, s, done.tk);
       }
-      run_reduce_partials(p1p, p2p, s1p, s2p, chunks, C, s1.options(), s);
+      if (!done.tk.cnt)
+        run_reduce_partials(p1p, p2p, s1p, s2p, chunks, C, s1.options(), s);
       if constexpr (OCT) {
         hipLaunchKernelGGL((bn_act_bwd_apply8_kernel<HS>),
             dim3(1, rows8_blocks(M, C)), dim3(256), 0, s, pdy, px, p.mean,
@@ -764,7 +1099,7 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
             (float)M, (int)act);
       }
     };
-    if (fast8_ok(xc, C)) {
+    if (fast8) {
       run(TypeTag<bf16>{}, std::true_type{});
     } else {
       with_dtype(xc, [&](auto tag) { run(tag, std::false_type{}); });

@@ -19,6 +19,7 @@
 // Requires Cin % 32 == 0 (every conv in the model except the 3-channel
 // stem, which has its own kernel in stem.hip).
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "conv_common.h"
@@ -34,65 +35,145 @@ namespace rthd {
 // reads w through explicit element strides so channels_last master
 // weights pack WITHOUT a contiguous() relayout first (that copy ran
 // twice per conv per training step — ~0.5 ms/step)
+
+// the master weight as the pack kernels read it
+struct PackSrc {
+  const float* w;
+  int Cout, Cin, KH, KW;
+  int64_t s0, s1, s2, s3;
+};
+
+// element i of one packed image. Rows/Rp: row count (+pad) of pk (= Cout or
+// Cin); Kp: padded k per tap
 template <typename T>
-__global__ void pack_weights_kernel(const float* __restrict__ w,
-                                    T* __restrict__ pk,
-                                    int Cout, int Cin, int KH, int KW,
-                                    int64_t s0, int64_t s1, int64_t s2,
-                                    int64_t s3,
+DEV_INLINE void pack_weight_elem(const PackSrc& a, T* __restrict__ pk,
+                                 int64_t i, int Rows, int Rp, int Kp,
+                                 int swap) {
+  const int t = i / ((int64_t)Rp * Kp);
+  const int row = (i / Kp) % Rp;
+  const int k = i % Kp;
+  float v = 0.f;
+  const int Kdim = swap ? a.Cout : a.Cin;
+  if (row < Rows && k < Kdim) {
+    int co, ci, ty, tx;
+    if (!swap) {
+      co = row; ci = k; ty = t / a.KW; tx = t % a.KW;
+    } else {
+      ci = row; co = k; ty = a.KH - 1 - t / a.KW; tx = a.KW - 1 - t % a.KW;
+    }
+    v = a.w[co * a.s0 + ci * a.s1 + ty * a.s2 + tx * a.s3];
+  }
+  stf(&pk[i], v);
+}
+
+template <typename T>
+__global__ void pack_weights_kernel(const PackSrc a, T* __restrict__ pk,
                                     int Rows, int Rp, int Kp, int swap) {
-  // Rows/Rp: row count (+pad) of pk (= Cout or Cin); Kp: padded k per tap
-  const int T_ = KH * KW;
-  const int64_t n = (int64_t)T_ * Rp * Kp;
+  const int64_t n = (int64_t)a.KH * a.KW * Rp * Kp;
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) pack_weight_elem(a, pk, i, Rows, Rp, Kp, swap);
+}
+
+// both images of one weight in one launch: index range [0, nf) is the
+// forward image (swap=false), [nf, nf + nd) the dgrad image (swap=true)
+template <typename TF, typename TD>
+__global__ void pack_weights_pair_kernel(const PackSrc a,
+                                         TF* __restrict__ pk,
+                                         TD* __restrict__ pkt, int Rpf,
+                                         int Kpf, int Rpd, int Kpd) {
+  const int64_t nf = (int64_t)a.KH * a.KW * Rpf * Kpf;
+  const int64_t n = nf + (int64_t)a.KH * a.KW * Rpd * Kpd;
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
-    const int t = i / ((int64_t)Rp * Kp);
-    const int row = (i / Kp) % Rp;
-    const int k = i % Kp;
-    float v = 0.f;
-    const int Kdim = swap ? Cout : Cin;
-    if (row < Rows && k < Kdim) {
-      int co, ci, ty, tx;
-      if (!swap) {
-        co = row; ci = k; ty = t / KW; tx = t % KW;
-      } else {
-        ci = row; co = k; ty = KH - 1 - t / KW; tx = KW - 1 - t % KW;
-      }
-      v = w[co * s0 + ci * s1 + ty * s2 + tx * s3];
-    }
-    stf(&pk[i], v);
+    if (i < nf) pack_weight_elem(a, pk, i, a.Cout, Rpf, Kpf, 0);
+    else pack_weight_elem(a, pkt, i - nf, a.Cin, Rpd, Kpd, 1);
   }
 }
 
-torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16) {
-  auto wc = w.to(at::kFloat);  // (Cout, Cin, KH, KW), any stride layout
+namespace {
+
+// geometry of one packed image of wc
+struct PackGeo {
+  int Rows, Rp, Kp;
+  int64_t n;
+};
+
+PackGeo pack_geo(const torch::Tensor& wc, bool swap) {
   const int Cout = wc.size(0), Cin = wc.size(1);
-  const int KH = wc.size(2), KW = wc.size(3);
-  const int T_ = KH * KW;
-  const int Rows = swap ? Cin : Cout;
+  const int T_ = wc.size(2) * wc.size(3);
+  PackGeo g;
+  g.Rows = swap ? Cin : Cout;
   const int Kdim = swap ? Cout : Cin;
-  const int Rp = (int)cdiv(Rows, 128) * 128;
+  g.Rp = (int)cdiv(g.Rows, 128) * 128;
   // K pads to 64 so the 64-ch-per-step kernel variant shares the same
   // packed image as the 32-ch ones (pad region is zeros)
-  const int Kp = (int)cdiv(Kdim, 64) * 64;
-  auto opt = wc.options().dtype(to_bf16 ? at::kBFloat16 : at::kFloat);
-  auto pk = torch::empty({T_, Rp, Kp}, opt);
-  const int64_t n = (int64_t)T_ * Rp * Kp;
-  auto s = at::cuda::getCurrentCUDAStream();
+  g.Kp = (int)cdiv(Kdim, 64) * 64;
+  g.n = (int64_t)T_ * g.Rp * g.Kp;
+  return g;
+}
+
+PackSrc pack_src(const torch::Tensor& wc) {
   const auto ws = wc.strides();
+  return {wc.data_ptr<float>(), (int)wc.size(0), (int)wc.size(1),
+          (int)wc.size(2), (int)wc.size(3), ws[0], ws[1], ws[2], ws[3]};
+}
+
+torch::Tensor pack_alloc(const torch::Tensor& wc, const PackGeo& g,
+                         bool to_bf16) {
+  return torch::empty({wc.size(2) * wc.size(3), g.Rp, g.Kp},
+      wc.options().dtype(to_bf16 ? at::kBFloat16 : at::kFloat));
+}
+
+}  // namespace
+
+torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16) {
+  auto wc = w.to(at::kFloat);  // (Cout, Cin, KH, KW), any stride layout
+  const PackGeo g = pack_geo(wc, swap);
+  auto pk = pack_alloc(wc, g, to_bf16);
+  auto s = at::cuda::getCurrentCUDAStream();
   if (to_bf16)
-    hipLaunchKernelGGL((pack_weights_kernel<bf16>), dim3(ew_grid(n, 256)),
-        dim3(256), 0, s, wc.data_ptr<float>(),
-        reinterpret_cast<bf16*>(pk.data_ptr()), Cout, Cin, KH, KW,
-        ws[0], ws[1], ws[2], ws[3], Rows, Rp, Kp, swap ? 1 : 0);
-  else
-    hipLaunchKernelGGL((pack_weights_kernel<float>), dim3(ew_grid(n, 256)),
-        dim3(256), 0, s, wc.data_ptr<float>(), pk.data_ptr<float>(),
-        Cout, Cin, KH, KW, ws[0], ws[1], ws[2], ws[3], Rows, Rp, Kp,
+    hipLaunchKernelGGL((pack_weights_kernel<bf16>), dim3(ew_grid(g.n, 256)),
+        dim3(256), 0, s, pack_src(wc),
+        reinterpret_cast<bf16*>(pk.data_ptr()), g.Rows, g.Rp, g.Kp,
         swap ? 1 : 0);
+  else
+    hipLaunchKernelGGL((pack_weights_kernel<float>), dim3(ew_grid(g.n, 256)),
+        dim3(256), 0, s, pack_src(wc), pk.data_ptr<float>(), g.Rows, g.Rp,
+        g.Kp, swap ? 1 : 0);
   HIP_CHECK_LAST();
   return pk;
+}
+
+// (pack_weights(w, false, to_bf16_fwd), pack_weights(w, true, to_bf16_dgrad))
+// from one launch: a training step needs both images of the same master
+// weight, the second one on the backward's critical path
+std::vector<torch::Tensor> pack_weights_pair(torch::Tensor w,
+                                             bool to_bf16_fwd,
+                                             bool to_bf16_dgrad) {
+  auto wc = w.to(at::kFloat);
+  const PackGeo gf = pack_geo(wc, false), gd = pack_geo(wc, true);
+  auto pk = pack_alloc(wc, gf, to_bf16_fwd);
+  auto pkt = pack_alloc(wc, gd, to_bf16_dgrad);
+  auto s = at::cuda::getCurrentCUDAStream();
+  const dim3 grid(ew_grid(gf.n + gd.n, 256));
+  auto launch = [&](auto* pf, auto* pd) {
+    using TF = std::remove_pointer_t<decltype(pf)>;
+    using TD = std::remove_pointer_t<decltype(pd)>;
+    hipLaunchKernelGGL((pack_weights_pair_kernel<TF, TD>), grid, dim3(256),
+        0, s, pack_src(wc), pf, pd, gf.Rp, gf.Kp, gd.Rp, gd.Kp);
+  };
+  bf16* fb = reinterpret_cast<bf16*>(pk.data_ptr());
+  bf16* db = reinterpret_cast<bf16*>(pkt.data_ptr());
+  float* ff = reinterpret_cast<float*>(pk.data_ptr());
+  float* df = reinterpret_cast<float*>(pkt.data_ptr());
+  if (to_bf16_fwd && to_bf16_dgrad) launch(fb, db);
+  else if (to_bf16_fwd) launch(fb, df);
+  else if (to_bf16_dgrad) launch(ff, db);
+  else launch(ff, df);
+  HIP_CHECK_LAST();
+  return {pk, pkt};
 }
 
 // ------------------------------ conv forward --------------------------------

@@ -289,6 +289,9 @@ void launch_small(const ConvGeo& g, const ConvOperands& o, int act,
 
 // python-visible entry points
 torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16);
+std::vector<torch::Tensor> pack_weights_pair(torch::Tensor w,
+                                             bool to_bf16_fwd,
+                                             bool to_bf16_dgrad);
 torch::Tensor pack_weights_fp8(torch::Tensor w);
 torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wpk,
                        torch::Tensor scale, torch::Tensor shift,

@@ -11,8 +11,9 @@ HIP kernels directly. Convolutions:
   [taps][Coutp][Cinp] bf16/f32) -> conv_fwd implicit GEMM with fused
   scale/shift/act epilogue. Training-mode BN splits into conv(linear) ->
   bn_stats -> bn_act_fwd; inference folds BN into the epilogue.
-- backward: dgrad = conv_fwd on dY with rotated/transposed packed weights;
-  wgrad = the transposed-staging MFMA kernel; BN/bias grads from the
+- backward: dgrad = conv_fwd on dY with rotated/transposed packed weights
+  (stride-1 convs pack that image in the forward's pack launch,
+  pack_weights_pair, and keep it on ctx); wgrad = the transposed-staging MFMA kernel; BN/bias grads from the
   reduction kernels.
 
 bf16 policy: when rthd.amp autocast is active (or inputs are bf16) compute
@@ -127,10 +128,18 @@ class _ConvBNActFn(torch.autograd.Function):
         # unfolded tensor is reused by the backward wgrad (which otherwise
         # re-unfolds).
         stem_col = is_stem and kh == 7
+        wpk_t = None
         if stem_col:
             xcol = C.stem_im2col(xc, kh, stride, pad)
             wpk = C.pack_weights(_stem_col_weight(weight), False, bf16)
             xc = xcol
+        elif stride == 1 and not is_stem and ctx.needs_input_grad[0]:
+            # the backward's dgrad needs the swapped image of the SAME
+            # weight: pack both now, in one launch, and keep the second —
+            # its own launch sat right ahead of the dgrad conv on the
+            # backward's critical path. The dgrad dtype rule is backward's.
+            wpk, wpk_t = C.pack_weights_pair(weight, bf16,
+                                             bf16 and cout % 8 == 0)
         else:
             wpk = C.pack_weights(weight, False, bf16)
 
@@ -197,6 +206,7 @@ class _ConvBNActFn(torch.autograd.Function):
                                   rvar.detach().clone())
         else:
             ctx.save_for_backward(xc, weight, y)
+        ctx.wpk_t = wpk_t
         return y
 
     @staticmethod
@@ -290,7 +300,9 @@ class _ConvBNActFn(torch.autograd.Function):
             ones, zeros = _ones_zeros(cin, xc.device)
             if stride == 1:
                 bf16_d = bf16 and dpre.shape[1] % 8 == 0
-                wpk_t = C.pack_weights(weight, True, bf16_d)
+                wpk_t = ctx.wpk_t  # packed by forward with wpk
+                if wpk_t is None:
+                    wpk_t = C.pack_weights(weight, True, bf16_d)
                 dsrc = dpre if bf16_d else dpre.float()
                 dx = C.conv_fwd(dsrc, wpk_t, ones, zeros, None, kh, kw, 1,
                                 pad, cin, ACT_CODE['Linear'])
