@@ -9,7 +9,7 @@ the 11 architecture flags from the checkpoint's sidecar pickle
 
 MI355X-specific additions live in their own group (``--engine``,
 ``--bucket-cap-mb``, ``--comm-dtype``, ``--channels-last``,
-``--device-encode``, ``--synthetic``):
+``--device-encode``, ``--device-augment``, ``--synthetic``):
 they control the HIP kernel engine and the RCCL-over-xGMI gradient bucketing
 and default to the MI355X-native path.
 """
@@ -186,6 +186,15 @@ def make_parser():
                  'boxes and the training device normalises the images and '
                  'encodes the heatmap/offset/size/mask targets (HIP kernels '
                  'on GPU) instead of numpy in the workers')
+    parser.add_argument('--device-augment', dest='device_augment',
+            action='store_true', default=False,
+            help='training only, implies --device-encode: the workers only '
+                 'decode, draw the augmentation parameters and move the '
+                 'boxes; brightness, affine, crop, flip and the batch '
+                 'resize run as one resampling kernel on the training '
+                 'device, which also writes the normalised image '
+                 '(single-pass bilinear: pixels differ slightly from the '
+                 'three-pass worker chain)')
     parser.add_argument('--synthetic', action='store_true', default=False,
             help='use synthetic VOC2028-shaped data (no dataset on disk)')
     parser.add_argument('--synthetic-size', type=int, default=512,
@@ -195,7 +204,10 @@ def make_parser():
 
 def build_parser(argv=None):
     """Parse argv (public interface parity: reference config.py:11-136)."""
-    return make_parser().parse_args(argv)
+    args = make_parser().parse_args(argv)
+    if args.device_augment:
+        args.device_encode = True
+    return args
 
 
 def seed_everything(seed):

@@ -11,6 +11,8 @@ from range(min,max,step) when multiscale is on, else max.
 Boxes are float (N,4) xyxy arrays + int (N,) label arrays throughout.
 """
 
+import collections
+
 import numpy as np
 from PIL import Image
 
@@ -110,6 +112,73 @@ def resize(img_np, boxes, size):
     return out, boxes
 
 
+class AugParams(collections.namedtuple(
+        'AugParams', 'factor scale tx ty top bottom left right flip')):
+    """One image's draws (TrainAugmentor.sample_params): brightness factor,
+    affine scale, translate in pixels, crop in pixels per side (all four 0
+    when the CPU path skips the crop) and the flip decision."""
+    __slots__ = ()
+
+
+def map_coefficients(params, size, target):
+    """Collapse resize <- flip <- crop <- affine into src = a * out + b per
+    axis, in continuous coordinates (pixel i centred at i + 0.5), composed
+    right to left from an output coordinate u of the (target, target) image:
+
+        resize:  u1 = u * (n / T)
+        flip:    u2 = n - u1              (x only, only when flipped)
+        crop:    u3 = c0 + u2 * (cn / n)
+        affine:  src = (u3 - n/2 - t) / s + n/2
+
+    Returns (ax, bx, ay, by) in float64; the caller rounds once to fp32."""
+    w, h = size
+    out = []
+    for n, t, c0, c1, flip in ((w, params.tx, params.left, params.right,
+                                params.flip),
+                               (h, params.ty, params.top, params.bottom,
+                                False)):
+        n = float(n)
+        f1, f0 = (-n / target, n) if flip else (n / target, 0.0)
+        k = (n - c0 - c1) / n
+        s = float(params.scale)
+        out.append(f1 * k / s)
+        out.append((c0 + f0 * k - n / 2.0 - t) / s + n / 2.0)
+    return tuple(out)
+
+
+def transform_boxes(boxes, labels, params, size, target):
+    """The box half of TrainAugmentor.__call__ for one image of ``size`` =
+    (w, h) under ``params``: affine, crop, flip, clip to the (w, h) canvas,
+    scale to (target, target) — the same fp32 arithmetic in the same order
+    as affine / crop_keep_size / fliplr / clip_boxes / resize above."""
+    w, h = size
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4).copy()
+    labels = np.asarray(labels, dtype=np.int64).reshape(-1)
+    if len(b):
+        s, cx, cy = params.scale, w / 2.0, h / 2.0
+        b[:, [0, 2]] = s * (b[:, [0, 2]] - cx) + cx + params.tx
+        b[:, [1, 3]] = s * (b[:, [1, 3]] - cy) + cy + params.ty
+        if params.top or params.bottom or params.left or params.right:
+            cw = w - params.left - params.right
+            ch = h - params.top - params.bottom
+            b[:, [0, 2]] = (b[:, [0, 2]] - params.left) * (w / cw)
+            b[:, [1, 3]] = (b[:, [1, 3]] - params.top) * (h / ch)
+        if params.flip:
+            x1 = w - b[:, 2]
+            x2 = w - b[:, 0]
+            b[:, 0], b[:, 2] = x1, x2
+        keep = (b[:, 2] > 0) & (b[:, 3] > 0) & (b[:, 0] < w) & (b[:, 1] < h)
+        b, labels = b[keep], labels[keep]
+        b[:, [0, 2]] = b[:, [0, 2]].clip(0, w)
+        b[:, [1, 3]] = b[:, [1, 3]].clip(0, h)
+        nonempty = (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+        b, labels = b[nonempty], labels[nonempty]
+    if len(b):
+        b[:, [0, 2]] *= target / w
+        b[:, [1, 3]] *= target / h
+    return b, labels
+
+
 class TrainAugmentor:
     """Multiply -> Affine -> Crop(keep_size) -> Fliplr -> clip -> batch resize."""
 
@@ -148,6 +217,36 @@ class TrainAugmentor:
             self._rng = np.random.RandomState(seed)
             self._worker_seed = wseed
         return self._rng
+
+    def sample_params(self, sizes):
+        """Draw what __call__ would draw for images of ``sizes`` [(w, h)...]
+        without touching a pixel: per image multiply, scale, tx, ty, top,
+        bottom, left, right, flip — the order __call__ consumes self.rng in
+        — then the multiscale choice once per batch. Returns
+        ([AugParams...], target)."""
+        rng = self.rng
+        tp = self.translate_percent
+        params = []
+        for w, h in sizes:
+            factor = rng.uniform(*self.color_multiply)
+            s = rng.uniform(self.affine_scale[0], self.affine_scale[1])
+            tx = rng.uniform(-tp, tp) * w
+            ty = rng.uniform(-tp, tp) * h
+            top = int(rng.uniform(*self.crop_percent) * h)
+            bottom = int(rng.uniform(*self.crop_percent) * h)
+            left = int(rng.uniform(*self.crop_percent) * w)
+            right = int(rng.uniform(*self.crop_percent) * w)
+            if top + bottom >= h or left + right >= w:
+                top = bottom = left = right = 0  # crop_keep_size skips it
+            flip = bool(rng.uniform() < 0.5)
+            params.append(AugParams(factor, s, tx, ty, top, bottom, left,
+                                    right, flip))
+        if self.multiscale_flag:
+            lo, hi, step = self.multiscale
+            target = int(rng.choice(np.arange(lo, hi, step)))
+        else:
+            target = int(self.multiscale[1])
+        return params, target
 
     def __call__(self, img_lst, boxes_lst, labels_lst):
         rng = self.rng

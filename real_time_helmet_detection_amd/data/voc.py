@@ -14,6 +14,9 @@ Capability parity with /root/reference/data.py:22-125:
 - ``collate_raw`` -> (img_u8, boxes, labels, voc_dict_list): the opt-in
   ``--device-encode`` form, which leaves normalisation and target encoding
   to the training device (ops.functional).
+- ``collate_device_aug`` -> (img_u8 canvas, sizes, coef, T, boxes, labels,
+  voc_dict_list): the opt-in ``--device-augment`` form, which leaves the
+  pixel half of the train augmentation to the device as well.
 
 ``SyntheticVOC`` generates VOC2028-shaped data in memory (random images,
 random plausible hat/person boxes, same voc_dict contract) for the
@@ -114,6 +117,58 @@ class _CollateMixin:
             list(imgs), list(boxes_lst), list(labels_lst))
         boxes_t, labels_t = pack_boxes(boxes_lst, labels_lst)
         return (torch.from_numpy(np.stack(imgs)), boxes_t, labels_t,
+                list(voc_dicts))
+
+    def collate_device_aug(self, batch):
+        """--device-augment: no pixel work in the worker. Draws the
+        TrainAugmentor parameters, moves the boxes with them and ships the
+        RAW images for ops.functional.augment_images to resample on the
+        training device:
+
+          img_u8 (B,Hmax,Wmax,3) uint8, each image in the top-left corner of
+                 a zero canvas of the batch-maximum size
+          sizes  (B,2) int32 [h, w]
+          coef   (B,5) fp32 [ax, bx, ay, by, factor] (augment.map_coefficients
+                 in float64, rounded once)
+          T      the batch's square target side
+          boxes (B,N,4) fp32 / labels (B,N) int32 in the (T, T) frame
+          voc_dict_list
+
+        An image whose longer side exceeds twice multiscale[1] is first
+        integer-reduced (box filter), its boxes divided by the same factor,
+        so the upload stays bounded whatever the dataset holds."""
+        from PIL import Image
+        from .augment import map_coefficients, transform_boxes
+        imgs, boxes_lst, labels_lst, voc_dicts = zip(*batch)
+        limit = 2 * int(self.transform.multiscale[1])
+        imgs, boxes_lst = list(imgs), list(boxes_lst)
+        for i, im in enumerate(imgs):
+            k = -(-max(im.shape[:2]) // limit)
+            if k > 1:
+                imgs[i] = np.asarray(
+                    Image.fromarray(np.ascontiguousarray(im)).reduce(k))
+                boxes_lst[i] = np.asarray(
+                    boxes_lst[i], dtype=np.float32).reshape(-1, 4) / k
+        sizes_wh = [(im.shape[1], im.shape[0]) for im in imgs]
+        params, target = self.transform.sample_params(sizes_wh)
+
+        hmax = max(h for _, h in sizes_wh)
+        wmax = max(w for w, _ in sizes_wh)
+        canvas = np.zeros((len(imgs), hmax, wmax, 3), dtype=np.uint8)
+        coef = np.zeros((len(imgs), 5), dtype=np.float32)
+        out_boxes, out_labels = [], []
+        for i, (im, p, wh) in enumerate(zip(imgs, params, sizes_wh)):
+            canvas[i, :wh[1], :wh[0]] = im
+            coef[i, :4] = map_coefficients(p, wh, target)
+            coef[i, 4] = p.factor
+            b, l = transform_boxes(boxes_lst[i], labels_lst[i], p, wh,
+                                   target)
+            out_boxes.append(b)
+            out_labels.append(l)
+        boxes_t, labels_t = pack_boxes(out_boxes, out_labels)
+        sizes = np.asarray([(h, w) for w, h in sizes_wh], dtype=np.int32)
+        return (torch.from_numpy(canvas), torch.from_numpy(sizes),
+                torch.from_numpy(coef), target, boxes_t, labels_t,
                 list(voc_dicts))
 
     def collate_fn(self, batch):

@@ -85,7 +85,9 @@ def distributed_worker(device, ngpus_per_node, args, env_launch=False):
         num_workers=num_workers,
         pin_memory=(dev.type == 'cuda'),
         sampler=sampler,
-        collate_fn=(dataset.collate_raw
+        collate_fn=(dataset.collate_device_aug
+                    if getattr(args, 'device_augment', False)
+                    else dataset.collate_raw
                     if getattr(args, 'device_encode', False)
                     else dataset.collate_fn),
         drop_last=False,
@@ -153,17 +155,43 @@ def prepare_batch(raw, dev, args, amp_on, use_cl):
     ops — HIP kernels on GPU, launched on the current stream ahead of (and
     outside) the captured train-step graph; box2hm/Normalizer on CPU. The
     image comes out bf16 under --amp (what the first conv casts to anyway)
-    and fp32 otherwise."""
+    and fp32 otherwise. With --device-augment ``raw`` is the six-tensor
+    ``collate_device_aug`` form instead (see _prepare_batch_augment)."""
     from ..ops import functional as opsF
-    img_u8, boxes, labels = (t.to(dev, non_blocking=True) for t in raw)
     dtype = torch.bfloat16 if (amp_on and dev.type == 'cuda') \
         else torch.float32
+    if getattr(args, 'device_augment', False):
+        return _prepare_batch_augment(raw, dev, args, dtype, use_cl)
+    img_u8, boxes, labels = (t.to(dev, non_blocking=True) for t in raw)
     image = opsF.normalize_images(img_u8, args.pretrained, dtype)
     if not use_cl:
         image = image.contiguous()
     targets = opsF.encode_targets(
         boxes, labels, tuple(img_u8.shape[1:3]), args.scale_factor,
         args.num_cls, args.normalized_coord)
+    return (image, *targets)
+
+
+def _prepare_batch_augment(raw, dev, args, dtype, use_cl):
+    """--device-augment: a ``collate_device_aug`` batch (raw uint8 canvas,
+    sizes, coefficients, T, boxes, labels) -> the same five tensors. The
+    uploads are the pixels, boxes and labels here and the two tiny
+    per-image tables (sizes, coefficients) inside augment_images, which
+    checks them on the host first; then augment_images — which resamples AND normalises, so normalize_images
+    drops out of this path — and encode_targets on the (T, T) frame. Same
+    stream and position as the --device-encode ops: ahead of and outside the
+    captured train-step graph."""
+    from ..ops import functional as opsF
+    img_u8, sizes, coef, target, boxes, labels = raw
+    img_u8, boxes, labels = (t.to(dev, non_blocking=True)
+                             for t in (img_u8, boxes, labels))
+    image = opsF.augment_images(img_u8, sizes, coef, target,
+                                args.pretrained, dtype)
+    if not use_cl:
+        image = image.contiguous()
+    targets = opsF.encode_targets(
+        boxes, labels, (target, target), args.scale_factor, args.num_cls,
+        args.normalized_coord)
     return (image, *targets)
 
 
@@ -206,7 +234,9 @@ def train_step(dataloader, network, loss_calculator, optimizer, scheduler,
                                    amp_on=(scaler is not None))
         network._rthd_graphed = graphed
 
-    device_encode = getattr(args, 'device_encode', False)
+    device_augment = getattr(args, 'device_augment', False)
+    device_encode = device_augment or getattr(args, 'device_encode', False)
+    n_raw = 6 if device_augment else 3  # tensors ahead of the voc dicts
 
     tictoc = time.time()
     for iteration, batch in enumerate(dataloader, 1):
@@ -218,7 +248,7 @@ def train_step(dataloader, network, loss_calculator, optimizer, scheduler,
         tictoc = time.time()
         if device_encode:
             image, gt_heatmap, gt_offset, gt_size, gt_mask = prepare_batch(
-                batch[:3], dev, args, scaler is not None, use_cl)
+                batch[:n_raw], dev, args, scaler is not None, use_cl)
         else:
             image, gt_heatmap, gt_offset, gt_size, gt_mask, gt_dict = batch
             image = image.to(dev, non_blocking=True)

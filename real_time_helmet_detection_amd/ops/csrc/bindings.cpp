@@ -118,6 +118,9 @@ std::vector<torch::Tensor> encode_targets(torch::Tensor boxes,
                                           int64_t num_cls, bool normalized);
 torch::Tensor normalize_u8(torch::Tensor img_u8, torch::Tensor table);
 int64_t encode_chunk();
+torch::Tensor augment_u8(torch::Tensor img_u8, torch::Tensor sizes,
+                         torch::Tensor coef, int64_t T,
+                         c10::optional<torch::Tensor> table);
 }  // namespace rthd
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -160,6 +163,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("encode_targets", &rthd::encode_targets);
   m.def("normalize_u8", &rthd::normalize_u8);
   m.def("encode_chunk", &rthd::encode_chunk);
+  m.def("augment_u8", &rthd::augment_u8, py::arg("img_u8"), py::arg("sizes"),
+        py::arg("coef"), py::arg("T"), py::arg("table") = py::none());
 }
 
 // ---------------------------------------------------------------------------

@@ -67,6 +67,77 @@ def normalize_images(img_u8, pretrained, dtype=torch.float32):
     return x.to(dtype).contiguous(memory_format=torch.channels_last)
 
 
+def _augment_axis(a, b, n, T):
+    """One axis of the augment map for outputs 0..T-1 of every image:
+    (clamped tap index 0, index 1, in-image mask 0, mask 1, weight), each
+    (B, T). a, b fp32 (B,), n int (B,)."""
+    i = torch.arange(T, dtype=torch.float32, device=a.device)
+    s = a[:, None] * (i + 0.5)[None, :] + b[:, None]
+    g = s - 0.5
+    nf = n.to(torch.float32)[:, None]
+    g = torch.minimum(torch.maximum(g, torch.full_like(g, -2.0)), nf + 1.0)
+    g0 = torch.floor(g)
+    f = g - g0
+    i0 = g0.to(torch.int64)
+    i1 = i0 + 1
+    n_ = n.to(torch.int64)[:, None]
+    m0 = (i0 >= 0) & (i0 < n_)
+    m1 = (i1 >= 0) & (i1 < n_)
+    zero = torch.zeros_like(i0)
+    c0 = torch.minimum(torch.maximum(i0, zero), n_ - 1)
+    c1 = torch.minimum(torch.maximum(i1, zero), n_ - 1)
+    return c0, c1, m0, m1, f
+
+
+def augment_images(img_u8, sizes, coef, T, pretrained=None,
+                   dtype=torch.float32):
+    """Train-time augmentation as one resample (the oracle of
+    ops/csrc/augment.hip, tap by tap in the kernel's order so the two can
+    be compared bit for bit).
+
+    img_u8 (B,Hmax,Wmax,3) uint8 with image b in its top-left sizes[b] =
+    [h, w] corner; coef (B,5) fp32 [ax, bx, ay, by, factor] from
+    data.augment.map_coefficients: source = a * output + b per axis in
+    continuous coordinates (pixel i centred at i + 0.5). Per output pixel,
+    every step rounded to fp32:
+
+        xs = a*(x + 0.5) + b;  g = xs - 0.5;  x0 = floor(g);  fx = g - x0
+        tap(p) = in the image ? min(floor(p * factor), 255) : 0
+        top = v00*(1-fx) + v01*fx;  bot = v10*(1-fx) + v11*fx
+        v = top*(1-fy) + bot*fy;  q = clamp(int(floor(v + 0.5)), 0, 255)
+
+    pretrained=None returns q as (B,T,T,3) uint8; otherwise
+    normalize_images(q, pretrained, dtype)."""
+    B = img_u8.shape[0]
+    T = int(T)
+    sizes = sizes.to(img_u8.device)
+    coef = coef.to(device=img_u8.device, dtype=torch.float32)
+    hmax, wmax = img_u8.shape[1:3]
+    h = sizes[:, 0].clamp(1, hmax)
+    w = sizes[:, 1].clamp(1, wmax)
+    cx0, cx1, mx0, mx1, fx = _augment_axis(coef[:, 0], coef[:, 1], w, T)
+    cy0, cy1, my0, my1, fy = _augment_axis(coef[:, 2], coef[:, 3], h, T)
+    factor = coef[:, 4].view(B, 1, 1, 1)
+    bi = torch.arange(B, device=img_u8.device).view(B, 1, 1)
+
+    def tap(cy, cx, my, mx):
+        p = img_u8[bi, cy[:, :, None], cx[:, None, :]].to(torch.float32)
+        val = torch.clamp(torch.floor(p * factor), max=255.0)
+        mask = (my[:, :, None] & mx[:, None, :]).to(torch.float32)
+        return val * mask[..., None]
+
+    fx = fx[:, None, :, None]
+    fy = fy[:, :, None, None]
+    gx, gy = 1.0 - fx, 1.0 - fy
+    top = tap(cy0, cx0, my0, mx0) * gx + tap(cy0, cx1, my0, mx1) * fx
+    bot = tap(cy1, cx0, my1, mx0) * gx + tap(cy1, cx1, my1, mx1) * fx
+    v = top * gy + bot * fy
+    q = torch.floor(v + 0.5).to(torch.int32).clamp(0, 255).to(torch.uint8)
+    if pretrained is None:
+        return q
+    return normalize_images(q, pretrained, dtype)
+
+
 # ---------------------------------------------------------------- conv-ish --
 
 def conv2d(x, weight, bias=None, stride=1, padding=0):

@@ -140,6 +140,23 @@ def normalize_images(img_u8, pretrained, dtype=torch.float32):
     return eager.normalize_images(img_u8, pretrained, dtype)
 
 
+def augment_images(img_u8, sizes, coef, T, pretrained=None,
+                   dtype=torch.float32):
+    """--device-augment: brightness, affine, crop, flip and the batch resize
+    of data.augment.TrainAugmentor as one resample of the raw batch.
+
+    img_u8 (B,Hmax,Wmax,3) uint8 canvas, sizes (B,2) int32 [h, w], coef
+    (B,5) fp32 [ax, bx, ay, by, factor], T the square output side. Returns
+    (B,T,T,3) uint8 when ``pretrained`` is None, else the normalised
+    (B,3,T,T) channels_last tensor of ``dtype`` — bit-identical to
+    normalize_images of the uint8 result."""
+    if _hip(img_u8):
+        from . import hip
+        return hip.augment_images(img_u8, sizes, coef, T, pretrained, dtype)
+    from . import eager
+    return eager.augment_images(img_u8, sizes, coef, T, pretrained, dtype)
+
+
 def upsample2x_add(x, skip=None):
     """Nearest 2x upsample, optionally fused with the hourglass skip add."""
     if _hip(x):

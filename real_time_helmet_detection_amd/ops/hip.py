@@ -717,6 +717,44 @@ def normalize_images(img_u8, pretrained, dtype=torch.float32):
                              _norm_table(img_u8.device, pretrained, dtype))
 
 
+def check_augment_args(img_u8, sizes, coef, T):
+    """Host-side argument checks of augment_images on the CPU copies of
+    ``sizes`` / ``coef`` (no device sync): every image fits its canvas and
+    every coefficient is finite."""
+    hmax, wmax = int(img_u8.shape[1]), int(img_u8.shape[2])
+    if int(T) < 1:
+        raise ValueError('augment_images: T must be >= 1, got %r' % (T,))
+    if sizes.numel():
+        h, w = sizes[:, 0], sizes[:, 1]
+        if int(h.min()) < 1 or int(h.max()) > hmax or int(w.min()) < 1 \
+                or int(w.max()) > wmax:
+            raise ValueError('augment_images: sizes must satisfy 1 <= h <= '
+                             '%d and 1 <= w <= %d' % (hmax, wmax))
+    if not bool(torch.isfinite(coef).all()):
+        raise ValueError('augment_images: non-finite coefficient')
+
+
+def augment_images(img_u8, sizes, coef, T, pretrained=None,
+                   dtype=torch.float32):
+    """Device twin of ops.eager.augment_images: one gather launch that
+    resamples the raw uint8 canvas batch to (T, T) under the per-image maps
+    and writes uint8 (pretrained=None) or the normalised channels_last
+    fp32 / bf16 image. ``sizes`` / ``coef`` still on the host are checked
+    there and uploaded; device copies are trusted (the kernel clamps every
+    address into the canvas regardless)."""
+    if pretrained is not None and dtype not in (torch.float32,
+                                                torch.bfloat16):
+        raise ValueError('augment_images: dtype must be float32 or '
+                         'bfloat16, got %r' % (dtype,))
+    if not sizes.is_cuda and not coef.is_cuda:
+        check_augment_args(img_u8, sizes, coef, T)
+    sizes = sizes.to(img_u8.device, non_blocking=True)
+    coef = coef.to(img_u8.device, non_blocking=True)
+    table = None if pretrained is None else \
+        _norm_table(img_u8.device, pretrained, dtype)
+    return _C().augment_u8(img_u8, sizes, coef, int(T), table)
+
+
 # ---------------------------------------------------------------- decode ---
 
 def batched_decode(heatmap, offset, wh, scale_factor, topk, pool_size,

@@ -10,6 +10,12 @@ machines); these are the available end-to-end proxies:
              held-out split every eval interval (does the pipeline
              generalize, not just memorize). VERDICT.md round-1 item 7.
 
+  holdout --augment device-encode | device-augment — the same, but every
+             training batch is drawn through TrainAugmentor and prepared by
+             trainer.prepare_batch the way main.py does under that flag
+             (same seed -> same draws: a paired comparison of the worker
+             PIL chain against the single-pass device resample).
+
 python tools/quality_probe.py [overfit|holdout] [--steps N] ...
 """
 import argparse
@@ -80,7 +86,13 @@ def main():
     ap.add_argument('--num-stack', type=int, default=1)
     ap.add_argument('--lr', type=float, default=2e-3)
     ap.add_argument('--eval-every', type=int, default=250)
+    ap.add_argument('--augment', default='none',
+                    choices=['none', 'device-encode', 'device-augment'],
+                    help='holdout: augment every training batch through '
+                         'the pipeline main.py uses under that flag')
     args = ap.parse_args()
+    if args.augment != 'none' and args.mode != 'holdout':
+        ap.error('--augment needs holdout mode')
 
     torch.manual_seed(0)
     if args.mode == 'overfit':
@@ -93,6 +105,25 @@ def main():
             args.train_imgs, args.size, seed=1000)
         val_items, (val_img, *_rest) = load_split(
             args.val_imgs, args.size, seed=2000)
+
+    aug_batch = None
+    if args.augment != 'none':
+        from real_time_helmet_detection_amd.config import build_parser
+        from real_time_helmet_detection_amd.data import TrainAugmentor
+        from real_time_helmet_detection_amd.engine.trainer import \
+            prepare_batch
+        pargs = build_parser(['--train-flag', '--amp', '--' + args.augment])
+        aug_ds = SyntheticVOC(
+            transform=TrainAugmentor(multiscale=(args.size, args.size, 64),
+                                     seed=17),
+            size=args.train_imgs, imsize=args.size, seed=1000)
+        collate = (aug_ds.collate_device_aug if pargs.device_augment
+                   else aug_ds.collate_raw)
+        dev = torch.device('cuda', torch.cuda.current_device())
+
+        def aug_batch(idx):
+            raw = collate([tr_items[i] for i in idx.tolist()])[:-1]
+            return prepare_batch(raw, dev, pargs, True, True)
 
     net = StackedHourglass(args.num_stack, args.in_ch, 6).cuda() \
         .to(memory_format=CL)
@@ -108,10 +139,15 @@ def main():
         idx = torch.randperm(n_train, generator=g)[:bs].cuda() \
             if args.mode == 'holdout' else slice(None)
         opt.zero_grad(set_to_none=True)
+        if aug_batch is not None:
+            b_img, b_hm, b_off, b_wh, b_mask = aug_batch(idx)
+        else:
+            b_img, b_hm, b_off, b_wh, b_mask = (img[idx], hm[idx], off[idx],
+                                                wh[idx], mask[idx])
         with amp.autocast(True):
-            out = net(img[idx])
-        total, _ = compute_stack_losses(out, calc, hm[idx], off[idx],
-                                        wh[idx], mask[idx], 2, False)
+            out = net(b_img)
+        total, _ = compute_stack_losses(out, calc, b_hm, b_off, b_wh,
+                                        b_mask, 2, False)
         total.backward()
         opt.step()
         if step % args.eval_every == 0:
