@@ -86,7 +86,12 @@ torch::Tensor stem_im2col(torch::Tensor x, int64_t KS, int64_t stride,
 torch::Tensor wgrad(torch::Tensor x, torch::Tensor dy, int64_t KH,
                     int64_t KW, int64_t stride, int64_t pad);
 torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
-                              int64_t KW, int64_t stride, int64_t pad);
+                              int64_t KW, int64_t stride, int64_t pad,
+                              const std::string& variant);
+torch::Tensor lds_tr16_selftest();
+std::string wgrad_bf16_choice(int64_t Cin, int64_t Cout, int64_t M);
+int64_t wgrad_bf16_chunk_len(int64_t Cin, int64_t Cout, int64_t taps,
+                             int64_t M);
 
 std::vector<torch::Tensor> conv_fwd_stats(
     torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
@@ -150,7 +155,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd_k64", &rthd::conv_fwd_k64);
   m.def("stem_im2col", &rthd::stem_im2col);
   m.def("wgrad", &rthd::wgrad);
-  m.def("wgrad_bf16_fast", &rthd::wgrad_bf16_fast);
+  m.def("wgrad_bf16_fast", &rthd::wgrad_bf16_fast,
+        py::arg("x"), py::arg("dy"), py::arg("kh"), py::arg("kw"),
+        py::arg("stride"), py::arg("pad"), py::arg("variant") = "");
+  m.def("lds_tr16_selftest", &rthd::lds_tr16_selftest);
+  m.def("wgrad_bf16_choice", &rthd::wgrad_bf16_choice);
+  m.def("wgrad_bf16_chunk_len", &rthd::wgrad_bf16_chunk_len);
   m.def("conv_fwd_stats", &rthd::conv_fwd_stats);
   m.def("bn_stats_from_parts", &rthd::bn_stats_from_parts,
         py::arg("p1"), py::arg("p2"), py::arg("running_mean") = py::none(),

@@ -16,8 +16,15 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
+#include "wgrad_tr_geo.h"
 
 namespace rthd {
+
+// conv.hip / wgrad_tr.hip
+const bf16* zero_page_bf16(const torch::Tensor& like);
+void wgrad_tr_launch(const WtrGeo& g, int nchunks, const bf16* x,
+                     const bf16* dy, const bf16* zpage, float* dwp,
+                     hipStream_t s);
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -298,8 +305,43 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part,
   }
 }
 
+// Kernel choice: the transposed-read kernel takes the aligned shapes
+// above 4096 px; RTHD_WGRAD_REGT=1 (read per call) forces the register-
+// transpose kernel. At and below 16^2 x B16 the launch dominates and the
+// old kernel's 64x64 tiles fill the chip better (us, 3x3 128ch, B16):
+//   px/image   regt    tr
+//   32^2       28.9    25.7
+//   16^2       18.5    20.2
+//   8^2        12.4    12.4
+// (full table: profiles/wgrad_tr.md)
+static bool wgrad_default_is_tr(int Cin, int Cout, int M) {
+  constexpr int kTrMinPx = 4096;
+  const char* e = getenv("RTHD_WGRAD_REGT");
+  const bool force_regt = e && atoi(e) != 0;
+  return Cin % 8 == 0 && Cout % 8 == 0 && !force_regt && M > kTrMinPx;
+}
+
+// "tr" or "regt": the kernel a default wgrad_bf16_fast call takes for these
+// channel counts and B*Ho*Wo pixels under the current environment
+std::string wgrad_bf16_choice(int64_t Cin, int64_t Cout, int64_t M) {
+  return wgrad_default_is_tr((int)Cin, (int)Cout, (int)M) ? "tr" : "regt";
+}
+
+// Pixel-chunk length both bf16 kernels run with: wtr_chunk_len
+// (wgrad_tr_geo.h) under RTHD_WGRAD_CHUNK, the perf-tuning knob (read per
+// call)
+int64_t wgrad_bf16_chunk_len(int64_t Cin, int64_t Cout, int64_t taps,
+                             int64_t M) {
+  int forced = 0;
+  if (const char* e = getenv("RTHD_WGRAD_CHUNK")) forced = atoi(e);
+  return wtr_chunk_len((int)M, (int)Cin, (int)Cout, (int)taps, forced);
+}
+
+// variant: "" = by rule, "regt" = the register-transpose kernel of this
+// file, "tr" = the transposed-read kernel of wgrad_tr.hip.
 torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
-                              int64_t KW, int64_t stride, int64_t pad) {
+                              int64_t KW, int64_t stride, int64_t pad,
+                              const std::string& variant) {
   auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
   auto dyc = dy.to(at::kBFloat16).contiguous(at::MemoryFormat::ChannelsLast);
   WgradGeo2 g;
@@ -316,18 +358,8 @@ torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
   const int ci_tiles = (int)cdiv(g.Cin, 64);
   const int co_tiles = (int)cdiv(g.Cout, 64);
   const int taps = (int)(KH * KW);
-  int nchunks = std::max(1, 1024 / (ci_tiles * co_tiles * taps));
-  int chunk_len = (int)cdiv(g.M, nchunks);
-  chunk_len = (int)cdiv(chunk_len, 128) * 128;
-  // 1x1 convs have no tap reuse to keep in L2 and prefer longer K runs
-  // per block: the chunk-size sweep measured 2048 fastest (65 us vs 82 at
-  // the formula's 1024 for 128ch @128^2).
-  if (taps == 1 && g.M >= 4096) chunk_len = std::max(chunk_len, 2048);
-  if (const char* e = getenv("RTHD_WGRAD_CHUNK")) {   // perf-tuning knob
-    const int v = atoi(e);
-    if (v >= 128) chunk_len = (int)cdiv(v, 128) * 128;
-  }
-  nchunks = (int)cdiv(g.M, chunk_len);
+  const int chunk_len = (int)wgrad_bf16_chunk_len(g.Cin, g.Cout, taps, g.M);
+  const int nchunks = (int)cdiv(g.M, chunk_len);
   g.chunk_len = chunk_len;
   g.ci_tiles = ci_tiles;
   g.co_tiles = co_tiles;
@@ -343,13 +375,34 @@ torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
   dim3 grid(ci_tiles, co_tiles, taps * nchunks);
   auto s = at::cuda::getCurrentCUDAStream();
   const bool aligned = (g.Cin % 8 == 0) && (g.Cout % 8 == 0);
+
+  bool use_tr = false;
+  if (variant == "tr") {
+    TORCH_CHECK(aligned, "wgrad_bf16_fast: variant 'tr' needs Cin % 8 == 0 "
+                "and Cout % 8 == 0");
+    use_tr = true;
+  } else if (variant.empty()) {
+    use_tr = wgrad_default_is_tr(g.Cin, g.Cout, g.M);
+  } else {
+    TORCH_CHECK(variant == "regt", "wgrad_bf16_fast: unknown variant '",
+                variant, "'");
+  }
   const bool same = stride == 1 && g.Ho == g.H && g.Wo == g.W;
   auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
   auto* pdy = reinterpret_cast<const bf16*>(dyc.data_ptr());
 #define RTHD_WG_LAUNCH(A_, S_)                                           \
   hipLaunchKernelGGL((wgrad_bf16_kernel<A_, S_>), grid, dim3(256), 0, s, \
       px, pdy, dwp.data_ptr<float>(), g)
-  if (aligned && same) RTHD_WG_LAUNCH(true, true);
+  if (use_tr) {
+    WtrGeo tg;
+    tg.B = g.B; tg.H = g.H; tg.W = g.W; tg.Cin = g.Cin;
+    tg.Ho = g.Ho; tg.Wo = g.Wo; tg.Cout = g.Cout;
+    tg.KH = g.KH; tg.KW = g.KW; tg.stride = g.stride; tg.pad = g.pad;
+    tg.M = g.M; tg.chunk_len = g.chunk_len;
+    wgrad_tr_launch(tg, nchunks, px, pdy, zero_page_bf16(xc),
+                    dwp.data_ptr<float>(), s);
+  }
+  else if (aligned && same) RTHD_WG_LAUNCH(true, true);
   else if (aligned)    RTHD_WG_LAUNCH(true, false);
   else if (same)       RTHD_WG_LAUNCH(false, true);
   else                 RTHD_WG_LAUNCH(false, false);

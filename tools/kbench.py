@@ -1,6 +1,7 @@
 """Micro-benchmark individual HIP kernels (A/B timing + rocprof target).
 
 python tools/kbench.py [wgrad|conv|stem_wgrad|bn|nms|all] [--iters N]
+    [--variant tr|regt]   (wgrad only)
 Prints per-kernel ms and effective TFLOP/s on the flagship shapes; ``nms``
 prints the hard/soft batched NMS kernels against their eager twins.
 """
@@ -31,20 +32,33 @@ def timeit(fn, iters=30, warmup=5):
     return s.elapsed_time(e) / iters
 
 
-def bench_wgrad(iters):
+def bench_wgrad(iters, variant=''):
+    # (name, B, cin, cout, hw, k, stride, pad): the first four are the
+    # historical table; the rest are the other wgrad shapes of the flagship
+    # step (64->128 is the stem-side residual, 152->64 the unfolded stem).
+    # The third row was labelled '128->64' until now; its arguments always
+    # were cin 64, cout 128, and only the label changed.
     shapes = [
         ('3x3 128ch @128^2 B16', 16, 128, 128, 128, 3, 1, 1),
         ('3x3 128ch @64^2 B16', 16, 128, 128, 64, 3, 1, 1),
-        ('3x3 128->64 @256^2 B16', 16, 64, 128, 256, 3, 1, 1),
+        ('3x3 64->128 @256^2 B16', 16, 64, 128, 256, 3, 1, 1),
         ('1x1 128ch @128^2 B16', 16, 128, 128, 128, 1, 1, 0),
+        ('1x1 152->64 @256^2 B16', 16, 152, 64, 256, 1, 1, 0),
+        ('1x1 128->64 @128^2 B16', 16, 128, 64, 128, 1, 1, 0),
+        ('3x3 64ch @128^2 B16', 16, 64, 64, 128, 3, 1, 1),
+        ('1x1 128->8 @128^2 B16', 16, 128, 8, 128, 1, 1, 0),
+        ('3x3 128ch @32^2 B16', 16, 128, 128, 32, 3, 1, 1),
+        ('3x3 128ch @16^2 B16', 16, 128, 128, 16, 3, 1, 1),
+        ('3x3 128ch @8^2 B16', 16, 128, 128, 8, 3, 1, 1),
     ]
+    print(f'wgrad variant: {variant or "default dispatch"}')
     for name, B, cin, cout, hw, k, stride, pad in shapes:
         x = torch.randn(B, cin, hw, hw, device='cuda',
                         dtype=torch.bfloat16).contiguous(memory_format=CL)
         dy = torch.randn(B, cout, hw, hw, device='cuda',
                          dtype=torch.bfloat16).contiguous(memory_format=CL)
-        ms = timeit(lambda: C.wgrad_bf16_fast(x, dy, k, k, stride, pad),
-                    iters)
+        ms = timeit(lambda: C.wgrad_bf16_fast(x, dy, k, k, stride, pad,
+                                              variant=variant), iters)
         fl = 2 * B * hw * hw * cin * cout * k * k
         print(f'wgrad {name:26s} {ms*1e3:8.1f}us  {fl/ms/1e9:7.1f} TF')
 
@@ -229,10 +243,15 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('which', nargs='?', default='all')
     ap.add_argument('--iters', type=int, default=30)
+    ap.add_argument('--variant', default='',
+                    choices=['', 'tr', 'regt'],
+                    help='wgrad kernel: tr = transposed-read, regt = '
+                         'register-transpose; default = the host dispatch '
+                         'rule')
     args = ap.parse_args()
     torch.manual_seed(0)
     if args.which in ('wgrad', 'all'):
-        bench_wgrad(args.iters)
+        bench_wgrad(args.iters, args.variant)
     if args.which in ('conv', 'all'):
         bench_conv(args.iters)
     if args.which in ('fp8', 'all'):
