@@ -30,7 +30,7 @@ if __name__ == '__main__':
         network=network, topk=args.topk, scale_factor=args.scale_factor,
         conf_th=args.conf_th, nms=args.nms, nms_th=args.nms_th,
         normalized_coord=args.normalized_coord,
-        pool_size=args.pool_size).to(device)
+        pool_size=args.pool_size, flip_test=args.flip_test).to(device)
     predictor.eval()
 
     img_ten, origin_size = imload(args.data, imsize, args.pretrained)

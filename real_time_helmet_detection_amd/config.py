@@ -11,7 +11,9 @@ MI355X-specific additions live in their own group (``--engine``,
 ``--bucket-cap-mb``, ``--comm-dtype``, ``--channels-last``,
 ``--device-encode``, ``--device-augment``, ``--synthetic``):
 they control the HIP kernel engine and the RCCL-over-xGMI gradient bucketing
-and default to the MI355X-native path.
+and default to the MI355X-native path. ``--flip-test`` (evaluation/demo
+group, default off) is an evaluation option, not an architecture flag: it is
+never restored from a checkpoint's sidecar.
 """
 
 import os
@@ -89,6 +91,12 @@ def make_parser():
             help='check_point path')
     parser.add_argument('--nms', type=str, default='nms',
             help='select nms algorithm (nms | soft-nms)')
+    parser.add_argument('--flip-test', dest='flip_test',
+            action='store_true', default=False,
+            help='flip testing: run the network on the image and on its '
+                 'horizontal mirror, average the two heatmaps and size '
+                 'maps (offsets from the plain image) and decode once; '
+                 'doubles the network batch')
     parser.add_argument('--fontsize', type=int, default=10,
             help='fontsize for demo, 0: do not write score/class in the image')
 

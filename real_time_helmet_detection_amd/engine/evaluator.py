@@ -65,11 +65,30 @@ def postprocess(p, boxes, clss, scores):
     raise NotImplementedError('Not expected nms algorithm: %s' % p.nms)
 
 
+def flip_test_decode(p, network, x):
+    """Flip test, shared by Prediction and GraphedPredictor: ONE network
+    pass over the batch and its horizontal mirror, then the logits-in
+    decode merges the two halves (mean heatmap and size, offsets from the
+    plain half). Returns boxes (B,S*topk,4), classes and scores
+    (B,S*topk)."""
+    out = network(torch.cat([x, x.flip(3)]))  # (2B, S, num_cls+4, h, w)
+    b, s = x.shape[0], out.shape[1]
+    boxes, clss, scores = ops.decode_logits(
+        out, p.scale_factor, p.topk, p.pool_size, p.normalized_coord,
+        flip=True)
+    return (boxes.reshape(b, s * p.topk, 4), clss.reshape(b, s * p.topk),
+            scores.reshape(b, s * p.topk))
+
+
 class Prediction(torch.nn.Module):
-    """network forward -> sigmoid -> batched decode -> per-item NMS."""
+    """network forward -> sigmoid -> batched decode -> per-item NMS.
+
+    ``flip_test`` averages the heatmap and size maps of the image and of
+    its horizontal mirror before the one decode (test-time augmentation;
+    the network batch doubles)."""
 
     def __init__(self, network, topk, scale_factor, conf_th, nms, nms_th,
-                 normalized_coord=False, pool_size=3):
+                 normalized_coord=False, pool_size=3, flip_test=False):
         super().__init__()
         self.network = network
         self.topk = topk
@@ -79,9 +98,12 @@ class Prediction(torch.nn.Module):
         self.nms_th = nms_th
         self.normalized_coord = normalized_coord
         self.pool_size = pool_size
+        self.flip_test = flip_test
 
     @torch.no_grad()
     def forward(self, x):
+        if self.flip_test:
+            return postprocess(self, *flip_test_decode(self, self.network, x))
         batch_output = self.network(x)  # (B, S, num_cls+4, h, w)
         b, s, c, h, w = batch_output.shape
         num_cls = c - 4
@@ -192,7 +214,8 @@ def single_device_evaluate(args):
         network=network, topk=args.topk, scale_factor=args.scale_factor,
         conf_th=args.conf_th, nms=args.nms, nms_th=args.nms_th,
         normalized_coord=args.normalized_coord,
-        pool_size=args.pool_size).to(device)
+        pool_size=args.pool_size,
+        flip_test=getattr(args, 'flip_test', False)).to(device)
 
     dataset = load_dataset(args)
     dataloader = torch.utils.data.DataLoader(
@@ -235,6 +258,10 @@ class GraphedPredictor(torch.nn.Module):
 
         def run(inp):
             with amp_ctx():
+                if getattr(p, 'flip_test', False):
+                    # mirror, concatenation, network and merge-decode are
+                    # all captured; static_in keeps the caller's shape
+                    return flip_test_decode(p, p.network, inp)
                 out = p.network(inp)
                 b, s2, c, h, w = out.shape
                 flat = out.reshape(b * s2, c, h, w).float()

@@ -85,15 +85,20 @@ class Export(torch.nn.Module):
     Returns (boxes, classes, scores) for the first batch item. ``nms``
     selects 'nms' (greedy IoU) or 'soft-nms' (Gaussian, sigma 0.5, drop at
     conf_th like ``Prediction``; returns the rescored scores).
+    ``flip_test`` runs the network on the image and its horizontal mirror
+    as a batch of two and decodes their merged maps once (``_forward_flip``);
+    input and outputs stay those of the one image.
     """
 
     def __init__(self, network, topk, scale_factor, conf_th, nms_th,
-                 normalized_coord=False, num_cls=2, pool_size=3, nms='nms'):
+                 normalized_coord=False, num_cls=2, pool_size=3, nms='nms',
+                 flip_test=False):
         super().__init__()
         if nms not in NMS_MODES:
             raise NotImplementedError(
                 'Not expected nms algorithm: %s' % nms)
         self.nms = nms
+        self.flip_test = flip_test
         self.network = network
         self.topk = topk
         self.scale_factor = scale_factor
@@ -104,6 +109,8 @@ class Export(torch.nn.Module):
         self.pool_size = pool_size
 
     def forward(self, x):
+        if self.flip_test:
+            return self._forward_flip(x)
         batch_output = self.network(x)  # (1, S, num_cls+4, h, w)
         outputs = batch_output[0]  # (S, num_cls+4, h, w)
         if outputs.is_cuda and not _backend.eager_gpu_override():
@@ -151,6 +158,9 @@ class Export(torch.nn.Module):
         b, c, s = torch.ops.rthd.decode(
             heatmap, offset, wh, self.scale_factor, self.topk,
             self.pool_size, self.normalized_coord)
+        return self._nms_native(b, c, s)
+
+    def _nms_native(self, b, c, s):
         boxes = b.reshape(-1, 4)
         clss = c.reshape(-1)
         scores = s.reshape(-1)
@@ -163,13 +173,43 @@ class Export(torch.nn.Module):
         keep = torch.ops.rthd.nms(boxes, scores, float(self.nms_th))
         return boxes[keep], clss[keep], scores[keep]
 
+    def _forward_flip(self, x):
+        """Flip test on the one input image: the network runs on a batch of
+        two (image, horizontal mirror) and the logits-in decode merges the
+        halves. GPU: rthd::decode_logits and the native NMS; CPU (or the
+        eager override): the eager composition and the scripted NMS."""
+        from ..ops import eager
+        out = self.network(torch.cat([x[:1], x[:1].flip(3)]))
+        if out.is_cuda and not _backend.eager_gpu_override():
+            if out.dtype != torch.bfloat16:
+                out = out.float()
+            b, c, s = torch.ops.rthd.decode_logits(
+                out.contiguous(), self.scale_factor, self.topk,
+                self.pool_size, self.normalized_coord, True)
+            return self._nms_native(b, c, s)
+        b, c, s = eager.decode_logits(
+            out, self.scale_factor, self.topk, self.pool_size,
+            self.normalized_coord, flip=True)
+        boxes = b.reshape(-1, 4)
+        clss = c.reshape(-1)
+        scores = s.reshape(-1)
+        keep = scores >= self.conf_th
+        boxes, clss, scores = boxes[keep], clss[keep], scores[keep]
+        if self.nms == 'soft-nms':
+            keep, rescored = soft_nms_scripted(boxes, scores, 0.5,
+                                               float(self.conf_th))
+            return boxes[keep], clss[keep], rescored
+        keep = nms_scripted(boxes, scores, self.nms_th)
+        return boxes[keep], clss[keep], scores[keep]
+
 
 def build_export_module(args, network):
     return Export(
         network=network, topk=args.topk, scale_factor=args.scale_factor,
         conf_th=args.conf_th, nms_th=args.nms_th,
         normalized_coord=args.normalized_coord, num_cls=args.num_cls,
-        pool_size=args.pool_size, nms=args.nms)
+        pool_size=args.pool_size, nms=args.nms,
+        flip_test=getattr(args, 'flip_test', False))
 
 
 def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,

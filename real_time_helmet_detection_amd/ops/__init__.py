@@ -48,6 +48,18 @@ def batched_decode(heatmap, offset, wh, scale_factor, topk, pool_size,
                                 pool_size, normalized)
 
 
+def decode_logits(out, scale_factor, topk, pool_size, normalized,
+                  flip=False):
+    # raw (Bt,S,C+4,h,w) network output in; flip=True merges the mirrored
+    # half B..2B-1 into the plain half (flip test)
+    if _hip(out):
+        from . import hip
+        return hip.decode_logits(out, scale_factor, topk, pool_size,
+                                 normalized, flip)
+    return eager.decode_logits(out, scale_factor, topk, pool_size,
+                               normalized, flip)
+
+
 def nms(boxes, scores, iou_threshold):
     if _hip(boxes):
         from . import hip

@@ -40,6 +40,10 @@ std::vector<torch::Tensor> decode_fwd(torch::Tensor hm, torch::Tensor off,
                                       torch::Tensor wh, int64_t scale_factor,
                                       int64_t topk, int64_t pool_size,
                                       bool normalized);
+std::vector<torch::Tensor> decode_logits(torch::Tensor out,
+                                         int64_t scale_factor, int64_t topk,
+                                         int64_t pool_size, bool normalized,
+                                         bool flip);
 torch::Tensor nms_fwd(torch::Tensor boxes, torch::Tensor scores,
                       double iou_threshold);
 std::vector<torch::Tensor> nms_batched(torch::Tensor boxes,
@@ -142,6 +146,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("centernet_loss_fused_fwd", &rthd::centernet_loss_fused_fwd);
   m.def("centernet_loss_fused_bwd", &rthd::centernet_loss_fused_bwd);
   m.def("decode_fwd", &rthd::decode_fwd);
+  m.def("decode_logits", &rthd::decode_logits);
   m.def("nms_fwd", &rthd::nms_fwd);
   m.def("nms_batched", &rthd::nms_batched);
   m.def("soft_nms", &rthd::soft_nms_fwd);
@@ -223,6 +228,13 @@ static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> decode_op(
                       scale_factor, topk, pool_size, normalized);
   return {v[0], v[1], v[2]};
 }
+static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+decode_logits_op(torch::Tensor out, int64_t scale_factor, int64_t topk,
+                 int64_t pool_size, bool normalized, bool flip) {
+  auto v = decode_logits(std::move(out), scale_factor, topk, pool_size,
+                         normalized, flip);
+  return {v[0], v[1], v[2]};
+}
 
 }  // namespace rthd
 
@@ -248,6 +260,9 @@ TORCH_LIBRARY(rthd, m) {
   m.def("decode(Tensor hm, Tensor off, Tensor wh, int scale_factor, "
         "int topk, int pool_size, bool normalized) "
         "-> (Tensor, Tensor, Tensor)");
+  m.def("decode_logits(Tensor out, int scale_factor, int topk, "
+        "int pool_size, bool normalized, bool flip) "
+        "-> (Tensor, Tensor, Tensor)");
   m.def("stem_im2col(Tensor x, int ks, int stride, int pad) -> Tensor");
 }
 
@@ -264,5 +279,6 @@ TORCH_LIBRARY_IMPL(rthd, CUDA, m) {
   m.impl("soft_nms", rthd::soft_nms_op);
   m.impl("soft_nms_batched", rthd::soft_nms_batched_op);
   m.impl("decode", rthd::decode_op);
+  m.impl("decode_logits", rthd::decode_logits_op);
   m.impl("stem_im2col", rthd::stem_im2col);
 }

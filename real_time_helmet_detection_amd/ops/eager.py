@@ -239,6 +239,49 @@ def batched_decode(heatmap, offset, wh, scale_factor, topk, pool_size,
     return boxes, clss, scores
 
 
+def decode_logits(out, scale_factor, topk, pool_size, normalized,
+                  flip=False):
+    """Decode the raw network output (Bt,S,C+4,h,w) — the oracle of the
+    logits-in kernel (ops/csrc/decode.hip, decode_logits).
+
+    flip=False: sigmoid on the heatmap channels (and on offset/size when
+    ``normalized``), then ``batched_decode`` with the stacks as batch.
+    flip=True (flip test): item B+b is the output for the horizontally
+    mirrored image b, B = Bt/2. In fp32, in this order: p = sigmoid,
+    hm = 0.5 * (p(plain) + p(mirrored).flip(-1)), size the same way (p only
+    when ``normalized``), offsets from the plain half alone — the mirrored
+    image's offsets point the other way (the CenterNet convention).
+    Returns (boxes (B*S,topk,4), classes (B*S,topk), scores (B*S,topk)).
+    """
+    bt, s, k, h, w = out.shape
+    c = k - 4
+    x = out.float()
+    if flip:
+        if int(bt) % 2:
+            raise ValueError('decode_logits: flip needs an even batch '
+                             '(plain half then mirrored half), got %d' % bt)
+        b = bt // 2
+        x, mirrored = x[:b], x[b:].flip(-1)
+    else:
+        b = bt
+    hm = torch.sigmoid(x[:, :, :c])
+    off = x[:, :, c:c + 2]
+    wh = x[:, :, c + 2:]
+    if normalized:
+        off = torch.sigmoid(off)
+        wh = torch.sigmoid(wh)
+    if flip:
+        hm = 0.5 * (hm + torch.sigmoid(mirrored[:, :, :c]))
+        wh_m = mirrored[:, :, c + 2:]
+        if normalized:
+            wh_m = torch.sigmoid(wh_m)
+        wh = 0.5 * (wh + wh_m)
+    return batched_decode(hm.reshape(b * s, c, h, w),
+                          off.reshape(b * s, 2, h, w),
+                          wh.reshape(b * s, 2, h, w),
+                          scale_factor, topk, pool_size, normalized)
+
+
 # ------------------------------------------------------------------- nms ----
 
 def box_iou(a, b):

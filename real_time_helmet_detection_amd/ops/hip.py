@@ -765,6 +765,26 @@ def batched_decode(heatmap, offset, wh, scale_factor, topk, pool_size,
     return boxes, clss, scores
 
 
+_DECODE_POOL_CAP = 7  # LDS halo of the tiled scan (decode.hip RMAX)
+
+
+def decode_logits(out, scale_factor, topk, pool_size, normalized,
+                  flip=False):
+    """Device twin of ops.eager.decode_logits: raw (Bt,S,C+4,h,w) logits,
+    bf16 or fp32, straight into the tiled decode — upcast, sigmoid and the
+    flip-test merge happen at the kernel's loads. Goes through the
+    dispatcher op so a trace records it."""
+    if pool_size > _DECODE_POOL_CAP:
+        # wider windows than the kernel's halo: the eager composition
+        from .eager import decode_logits as eager_dl
+        return eager_dl(out, scale_factor, topk, pool_size, normalized, flip)
+    if out.dtype not in (torch.float32, torch.bfloat16):
+        out = out.float()
+    return _ops().decode_logits(out.contiguous(), int(scale_factor),
+                                int(topk), int(pool_size), bool(normalized),
+                                bool(flip))
+
+
 _NMS_CAP = 2048  # LDS-resident kernel limit (nms.hip)
 
 

@@ -1,9 +1,10 @@
 """Micro-benchmark individual HIP kernels (A/B timing + rocprof target).
 
-python tools/kbench.py [wgrad|conv|stem_wgrad|bn|nms|all] [--iters N]
+python tools/kbench.py [wgrad|conv|stem_wgrad|bn|nms|decode|all] [--iters N]
     [--variant tr|regt]   (wgrad only)
 Prints per-kernel ms and effective TFLOP/s on the flagship shapes; ``nms``
-prints the hard/soft batched NMS kernels against their eager twins.
+prints the hard/soft batched NMS kernels against their eager twins,
+``decode`` the logits-in decode against the composition it replaces.
 """
 import argparse
 import os
@@ -239,6 +240,55 @@ def bench_nms(iters):
                          e_ms / k_ms))
 
 
+def decode_composition(out, flip, topk):
+    """What decode_logits replaces, from existing ops only: upcast, split,
+    sigmoid, (flip, add, scale), then the maps-in decode_fwd."""
+    bt, s, k, h, w = out.shape
+    flat = out.reshape(bt * s, k, h, w).float()
+    hm, off, wh = flat.split([k - 4, 2, 2], dim=1)
+    hm = torch.sigmoid(hm)
+    if flip:
+        n = bt * s // 2
+        hm = 0.5 * (hm[:n] + hm[n:].flip(-1))
+        wh = 0.5 * (wh[:n] + wh[n:].flip(-1))
+        off = off[:n]
+    return C.decode_fwd(hm, off, wh, 4, topk, 3, False)
+
+
+def bench_decode(iters, rounds=9):
+    """decode_logits against decode_composition on bf16 logits
+    (Bt,1,6,128,128), images B of 1 and 8, flip off and on. A and B
+    alternate round by round on warm kernels; prints the median and the
+    min..max of the rounds (us per call, device time) and the ratio of
+    the medians."""
+    import statistics
+    topk = 100
+    print('decode: fused decode_logits (A) vs composition + decode_fwd (B),'
+          ' bf16 (Bt,1,6,128,128), topk %d, %d rounds x %d calls'
+          % (topk, rounds, iters))
+    print('%2s %5s %30s %30s %7s'
+          % ('B', 'flip', 'A us med (min..max)', 'B us med (min..max)',
+             'B/A'))
+    for b in (1, 8):
+        for flip in (False, True):
+            bt = 2 * b if flip else b
+            g = torch.Generator().manual_seed(100 * b + flip)
+            out = (torch.randn(bt, 1, 6, 128, 128, generator=g) * 2 - 2) \
+                .to(torch.bfloat16).cuda()
+            fa = lambda: C.decode_logits(out, 4, topk, 3, False, flip)  # noqa
+            fb = lambda: decode_composition(out, flip, topk)  # noqa
+            ta, tb = [], []
+            timeit(fa, iters)
+            timeit(fb, iters)
+            for _ in range(rounds):
+                ta.append(timeit(fa, iters, warmup=2) * 1e3)
+                tb.append(timeit(fb, iters, warmup=2) * 1e3)
+            ma, mb = statistics.median(ta), statistics.median(tb)
+            print('%2d %5s %12.1f (%6.1f..%6.1f) %14.1f (%6.1f..%6.1f) %6.2fx'
+                  % (b, flip, ma, min(ta), max(ta), mb, min(tb), max(tb),
+                     mb / ma))
+
+
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('which', nargs='?', default='all')
@@ -262,3 +312,5 @@ if __name__ == '__main__':
         bench_bn(args.iters)
     if args.which in ('nms', 'all'):
         bench_nms(args.iters)
+    if args.which in ('decode', 'all'):
+        bench_decode(args.iters)

@@ -16,6 +16,10 @@ machines); these are the available end-to-end proxies:
              (same seed -> same draws: a paired comparison of the worker
              PIL chain against the single-pass device resample).
 
+  --flip-test — evaluate through Prediction(flip_test=True); training is
+             untouched, so a run with and one without the flag (same seed)
+             score the same weights.
+
 python tools/quality_probe.py [overfit|holdout] [--steps N] ...
 """
 import argparse
@@ -46,10 +50,11 @@ def load_split(n, size, seed):
                    *(t.cuda() for t in (hm, off, wh, mask)))
 
 
-def eval_map(net, items, img, conf_th=0.15, topk=20, fp8=False):
+def eval_map(net, items, img, conf_th=0.15, topk=20, fp8=False,
+             flip_test=False):
     net.eval()
     pred = Prediction(net, topk=topk, scale_factor=4, conf_th=conf_th,
-                      nms='nms', nms_th=0.5).cuda()
+                      nms='nms', nms_th=0.5, flip_test=flip_test).cuda()
     gt, preds = {}, {}
     import contextlib
     fp8_ctx = amp.fp8_autocast(True) if fp8 else contextlib.nullcontext()
@@ -90,6 +95,9 @@ def main():
                     choices=['none', 'device-encode', 'device-augment'],
                     help='holdout: augment every training batch through '
                          'the pipeline main.py uses under that flag')
+    ap.add_argument('--flip-test', action='store_true',
+                    help='evaluate with flip testing (same training run: '
+                         'pair it with a run without the flag, same seed)')
     args = ap.parse_args()
     if args.augment != 'none' and args.mode != 'holdout':
         ap.error('--augment needs holdout mode')
@@ -151,19 +159,27 @@ def main():
         total.backward()
         opt.step()
         if step % args.eval_every == 0:
-            m = eval_map(net, val_items, val_img)
+            m = eval_map(net, val_items, val_img, flip_test=args.flip_test)
             row = {'step': step, 'loss': round(float(total.item()), 4),
                    'val_map@0.5' if args.mode == 'holdout' else 'map@0.5':
                        round(m, 4)}
+            if args.flip_test:
+                # the same weights without the mirror pass: the pair is
+                # exact even where two training runs are not
+                row['val_map@0.5_plain' if args.mode == 'holdout'
+                    else 'map@0.5_plain'] = round(
+                        eval_map(net, val_items, val_img), 4)
             if args.mode == 'holdout':
                 row['train_map@0.5'] = round(
                     eval_map(net, tr_items[:args.val_imgs],
-                             img[:args.val_imgs]), 4)
+                             img[:args.val_imgs],
+                             flip_test=args.flip_test), 4)
                 if args.in_ch % 128 == 0:
                     # fp8-resident serving quality on the same held-out
                     # split (VERDICT round-1 item 6: fp8 mAP probe)
                     row['val_map@0.5_fp8'] = round(
-                        eval_map(net, val_items, val_img, fp8=True), 4)
+                        eval_map(net, val_items, val_img, fp8=True,
+                                 flip_test=args.flip_test), 4)
             curve.append(row)
             print(json.dumps(row), flush=True)
     print(json.dumps({'mode': args.mode, 'final': curve[-1] if curve
