@@ -493,8 +493,9 @@ namespace {
 
 // variants: 0 = the 128x128/K32 kernel of this file, 1 = 64x64 split-K
 // (small spatial / Cout<=64 fill), 2 = 128x128/K64 double-buffer (fewer
-// barriers+glds issues per channel)
-struct ConvChoice { int small; int splitk; };
+// barriers+glds issues per channel), 3 = halo-tile 3x3 (conv_halo.hip; it
+// has no stats epilogue: conv_fwd_stats then runs `alt`, the faster of 0/2)
+struct ConvChoice { int small; int splitk; int alt = 0; };
 
 std::mutex g_conv_tune_mu;
 std::unordered_map<uint64_t, ConvChoice> g_conv_tune;
@@ -505,6 +506,9 @@ uint64_t conv_key(const ConvGeo& g) {
     h ^= v + 0x9e3779b97f4a7c15ull + (h << 6) + (h >> 2);
   };
   mix(g.M); mix(g.Cin); mix(g.Cout); mix(g.KH); mix(g.KW); mix(g.stride);
+  // M does not fix H, W or pad, which decide whether the halo variant may
+  // be a shape's cached choice
+  mix(halo_eligible(g));
   return h;
 }
 
@@ -586,7 +590,10 @@ ConvChoice choose_conv_variant(const ConvGeo& g, const ConvOperands& o,
   auto s = at::cuda::getCurrentCUDAStream();
   if (stream_capturing(s) || getenv("RTHD_NO_AUTOTUNE")) {
     if (big_blocks >= 512 && g.Cout > 64) {
-      ch = {0, 1};
+      // the halo variant measured ahead of both 128-tile kernels on every
+      // eligible shape of this size (profiles/conv_halo.md)
+      if (halo_eligible(g)) ch = {3, 1, 0};
+      else                  ch = {0, 1};
     } else if (!cands.empty()) {
       ch = {1, cands.back()};
       for (int sk : cands) {
@@ -599,10 +606,15 @@ ConvChoice choose_conv_variant(const ConvGeo& g, const ConvOperands& o,
     const float tk = time_usec(
         [&] { launch_k64(g, o, act, nullptr, nullptr); }, s.stream());
     if (tk < best) { best = tk; ch = {2, 1}; }
+    const int alt = ch.small;
     for (int sk : cands) {
       const float t = time_usec(
           [&] { launch_small(g, o, act, sk); }, s.stream());
       if (t < best) { best = t; ch = {1, sk}; }
+    }
+    if (halo_eligible(g)) {
+      const float t = time_usec([&] { launch_halo(g, o, act); }, s.stream());
+      if (t < best) { best = t; ch = {3, 1, alt}; }
     }
   }
   std::lock_guard<std::mutex> lk(g_conv_tune_mu);
@@ -630,6 +642,7 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wpk,
     const ConvChoice ch = choose_conv_variant(g, o, (int)act);
     if (ch.small == 1)      launch_small(g, o, (int)act, ch.splitk);
     else if (ch.small == 2) launch_k64(g, o, (int)act, nullptr, nullptr);
+    else if (ch.small == 3) launch_halo(g, o, (int)act);
     else                    launch_big(g, o, (int)act, nullptr, nullptr);
     return o.y;
   }
@@ -677,7 +690,10 @@ std::vector<torch::Tensor> conv_fwd_stats(
   auto p1 = torch::empty({2 * cdiv(g.M, 128), Cout},
                          o.x.options().dtype(at::kFloat));
   auto p2 = torch::empty_like(p1);
-  if (ch.small == 2)
+  // the halo variant has no stats epilogue: its shapes keep the faster of
+  // the two 128-tile kernels here
+  const int variant = ch.small == 3 ? ch.alt : ch.small;
+  if (variant == 2)
     launch_k64(g, o, (int)act, p1.data_ptr<float>(), p2.data_ptr<float>());
   else
     launch_big(g, o, (int)act, p1.data_ptr<float>(), p2.data_ptr<float>());

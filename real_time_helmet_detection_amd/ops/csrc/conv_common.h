@@ -286,6 +286,9 @@ void launch_k64(const ConvGeo& g, const ConvOperands& o, int act,
                 float* p1, float* p2);                      // conv_k64.hip
 void launch_small(const ConvGeo& g, const ConvOperands& o, int act,
                   int splitk);                              // conv_small.hip
+// halo-tile 3x3 variant: the shapes it takes, and its launcher (no stats)
+bool halo_eligible(const ConvGeo& g);                       // conv_halo.hip
+void launch_halo(const ConvGeo& g, const ConvOperands& o, int act);
 
 // python-visible entry points
 torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16);
@@ -307,6 +310,11 @@ torch::Tensor conv_fwd_k64(torch::Tensor x, torch::Tensor wpk,
                            c10::optional<torch::Tensor> skip,
                            int64_t KH, int64_t KW, int64_t stride,
                            int64_t pad, int64_t Cout, int64_t act);
+torch::Tensor conv_fwd_halo(torch::Tensor x, torch::Tensor wpk,
+                            torch::Tensor scale, torch::Tensor shift,
+                            c10::optional<torch::Tensor> skip,
+                            int64_t KH, int64_t KW, int64_t stride,
+                            int64_t pad, int64_t Cout, int64_t act);
 torch::Tensor conv_fwd_small(torch::Tensor x, torch::Tensor wpk,
                              torch::Tensor scale, torch::Tensor shift,
                              c10::optional<torch::Tensor> skip,

@@ -73,6 +73,9 @@ def bench_conv(iters):
         ('3x3 128ch @16^2 B16', 16, 128, 128, 16, 3, 1, 1),
         ('3x3 128ch @8^2 B16', 16, 128, 128, 8, 3, 1, 1),
         ('1x1 128ch @128^2 B16', 16, 128, 128, 128, 1, 1, 0),
+        # the stem-side 3x3 pair of the flagship step (forward and dgrad)
+        ('3x3 64->128 @256^2 B16', 16, 64, 128, 256, 3, 1, 1),
+        ('3x3 128->64 @256^2 B16', 16, 128, 64, 256, 3, 1, 1),
     ]
     for name, B, cin, cout, hw, k, stride, pad in shapes:
         x = torch.randn(B, cin, hw, hw, device='cuda',
@@ -95,6 +98,15 @@ def bench_conv(iters):
                   f'{fl/ms/1e9:7.1f} TF')
         except RuntimeError as e:
             print(f'conv(k64) {name}: {e}')
+        if k == 3:
+            try:
+                ms = timeit(lambda: C.conv_fwd_halo(x, wpk, ones, zeros,
+                                                    None, k, k, stride, pad,
+                                                    cout, 1), iters)
+                print(f'conv(halo) {name:26s} {ms*1e3:8.1f}us  '
+                      f'{fl/ms/1e9:7.1f} TF')
+            except RuntimeError:
+                print(f'conv(halo) {name}: not a multiple of the 8x16 tile')
         for sk in (1, 2, 4, 8, 16):
             if sk > 9 * max(1, cin // 32):
                 continue
