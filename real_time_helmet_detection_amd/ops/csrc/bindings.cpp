@@ -99,6 +99,10 @@ torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
                               const std::string& variant);
 torch::Tensor lds_tr16_selftest();
 std::string wgrad_bf16_choice(int64_t Cin, int64_t Cout, int64_t M);
+std::string wgrad_bf16_choice_geo(int64_t Cin, int64_t Cout, int64_t KH,
+                                  int64_t KW, int64_t stride, int64_t pad,
+                                  int64_t H, int64_t W, int64_t B);
+int64_t wgrad_row_chunk_len(int64_t Cin, int64_t Cout, int64_t M);
 int64_t wgrad_bf16_chunk_len(int64_t Cin, int64_t Cout, int64_t taps,
                              int64_t M);
 
@@ -172,6 +176,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lds_tr16_selftest", &rthd::lds_tr16_selftest);
   m.def("wgrad_bf16_choice", &rthd::wgrad_bf16_choice);
   m.def("wgrad_bf16_chunk_len", &rthd::wgrad_bf16_chunk_len);
+  m.def("wgrad_bf16_choice_geo", &rthd::wgrad_bf16_choice_geo,
+        py::arg("cin"), py::arg("cout"), py::arg("kh"), py::arg("kw"),
+        py::arg("stride"), py::arg("pad"), py::arg("h"), py::arg("w"),
+        py::arg("b"));
+  m.def("wgrad_row_chunk_len", &rthd::wgrad_row_chunk_len);
   m.def("conv_fwd_stats", &rthd::conv_fwd_stats);
   m.def("bn_stats_from_parts", &rthd::bn_stats_from_parts,
         py::arg("p1"), py::arg("p2"), py::arg("running_mean") = py::none(),

@@ -16,15 +16,18 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 #include "common.h"
-#include "wgrad_tr_geo.h"
+#include "wgrad_row_geo.h"
 
 namespace rthd {
 
-// conv.hip / wgrad_tr.hip
+// conv.hip / wgrad_tr.hip / wgrad_row.hip
 const bf16* zero_page_bf16(const torch::Tensor& like);
 void wgrad_tr_launch(const WtrGeo& g, int nchunks, const bf16* x,
                      const bf16* dy, const bf16* zpage, float* dwp,
                      hipStream_t s);
+void wgrad_row_launch(const WtrGeo& g, int nchunks, const bf16* x,
+                      const bf16* dy, const bf16* zpage, float* dwp,
+                      hipStream_t s);
 
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -327,7 +330,52 @@ std::string wgrad_bf16_choice(int64_t Cin, int64_t Cout, int64_t M) {
   return wgrad_default_is_tr((int)Cin, (int)Cout, (int)M) ? "tr" : "regt";
 }
 
-// Pixel-chunk length both bf16 kernels run with: wtr_chunk_len
+// The tap-row kernel (wgrad_row.hip) takes the 3x3 stride-1 pad-1 shapes it
+// can compute (wrow_eligible) with at least 64 channels on both sides
+// (below that its 64 x 128 tile is mostly zero columns) above 65536 px: its
+// wide tiles need long pixel runs to fill the chip (us, 3x3, B16, with the
+// reduce; full table in profiles/wgrad_row.md):
+//   shape             tr      row
+//   128ch @256^2      558     375
+//   64->128 @256^2    292     219
+//   128ch @128^2      171     137
+//   128ch @64^2       51.7    70.6
+//   128ch @32^2       25.6    53.5
+// RTHD_WGRAD_ROW=0 (read per call) returns every shape to the rule above,
+// RTHD_WGRAD_REGT=1 keeps its meaning.
+static bool wgrad_default_is_row(const WtrGeo& g) {
+  constexpr int kRowMinPx = 65536;
+  const char* e = getenv("RTHD_WGRAD_ROW");
+  if (e && atoi(e) == 0) return false;
+  return wrow_eligible(g) && g.Cin >= 64 && g.Cout >= 64 &&
+         g.M > kRowMinPx && wgrad_default_is_tr(g.Cin, g.Cout, g.M);
+}
+
+static WtrGeo wgrad_geo(int64_t B, int64_t Cin, int64_t H, int64_t W,
+                        int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                        int64_t pad) {
+  WtrGeo g;
+  g.B = (int)B; g.H = (int)H; g.W = (int)W; g.Cin = (int)Cin;
+  g.Cout = (int)Cout;
+  g.KH = (int)KH; g.KW = (int)KW; g.stride = (int)stride; g.pad = (int)pad;
+  g.Ho = (int)((H + 2 * pad - KH) / stride + 1);
+  g.Wo = (int)((W + 2 * pad - KW) / stride + 1);
+  g.M = g.B * g.Ho * g.Wo;
+  g.chunk_len = 0;
+  return g;
+}
+
+// "row", "tr" or "regt": the kernel a default wgrad_bf16_fast call takes
+// for a [B, Cin, H, W] input of a KH x KW conv under the current environment
+std::string wgrad_bf16_choice_geo(int64_t Cin, int64_t Cout, int64_t KH,
+                                  int64_t KW, int64_t stride, int64_t pad,
+                                  int64_t H, int64_t W, int64_t B) {
+  const WtrGeo g = wgrad_geo(B, Cin, H, W, Cout, KH, KW, stride, pad);
+  if (wgrad_default_is_row(g)) return "row";
+  return wgrad_bf16_choice(Cin, Cout, g.M);
+}
+
+// Pixel-chunk length the regt and tr kernels run with: wtr_chunk_len
 // (wgrad_tr_geo.h) under RTHD_WGRAD_CHUNK, the perf-tuning knob (read per
 // call)
 int64_t wgrad_bf16_chunk_len(int64_t Cin, int64_t Cout, int64_t taps,
@@ -337,8 +385,17 @@ int64_t wgrad_bf16_chunk_len(int64_t Cin, int64_t Cout, int64_t taps,
   return wtr_chunk_len((int)M, (int)Cin, (int)Cout, (int)taps, forced);
 }
 
+// ... and the tap-row kernel's: wrow_chunk_len (wgrad_row_geo.h) under the
+// same override
+int64_t wgrad_row_chunk_len(int64_t Cin, int64_t Cout, int64_t M) {
+  int forced = 0;
+  if (const char* e = getenv("RTHD_WGRAD_CHUNK")) forced = atoi(e);
+  return wrow_chunk_len((int)M, (int)Cin, (int)Cout, forced);
+}
+
 // variant: "" = by rule, "regt" = the register-transpose kernel of this
-// file, "tr" = the transposed-read kernel of wgrad_tr.hip.
+// file, "tr" = the transposed-read kernel of wgrad_tr.hip, "row" = the
+// tap-row kernel of wgrad_row.hip.
 torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
                               int64_t KW, int64_t stride, int64_t pad,
                               const std::string& variant) {
@@ -355,10 +412,36 @@ torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
   g.KH = KH; g.KW = KW; g.stride = stride; g.pad = pad;
   g.M = g.B * g.Ho * g.Wo;
 
+  const bool aligned = (g.Cin % 8 == 0) && (g.Cout % 8 == 0);
+  WtrGeo tg;
+  tg.B = g.B; tg.H = g.H; tg.W = g.W; tg.Cin = g.Cin;
+  tg.Ho = g.Ho; tg.Wo = g.Wo; tg.Cout = g.Cout;
+  tg.KH = g.KH; tg.KW = g.KW; tg.stride = g.stride; tg.pad = g.pad;
+  tg.M = g.M;
+
+  bool use_tr = false, use_row = false;
+  if (variant == "row") {
+    TORCH_CHECK(wrow_eligible(tg), "wgrad_bf16_fast: variant 'row' needs a "
+                "3x3 stride-1 pad-1 conv with Wo % 32 == 0, Cin % 8 == 0 and "
+                "Cout % 8 == 0");
+    use_row = true;
+  } else if (variant == "tr") {
+    TORCH_CHECK(aligned, "wgrad_bf16_fast: variant 'tr' needs Cin % 8 == 0 "
+                "and Cout % 8 == 0");
+    use_tr = true;
+  } else if (variant.empty()) {
+    use_row = wgrad_default_is_row(tg);
+    use_tr = !use_row && wgrad_default_is_tr(g.Cin, g.Cout, g.M);
+  } else {
+    TORCH_CHECK(variant == "regt", "wgrad_bf16_fast: unknown variant '",
+                variant, "'");
+  }
+
   const int ci_tiles = (int)cdiv(g.Cin, 64);
   const int co_tiles = (int)cdiv(g.Cout, 64);
   const int taps = (int)(KH * KW);
-  const int chunk_len = (int)wgrad_bf16_chunk_len(g.Cin, g.Cout, taps, g.M);
+  int chunk_len = (int)wgrad_bf16_chunk_len(g.Cin, g.Cout, taps, g.M);
+  if (use_row) chunk_len = (int)wgrad_row_chunk_len(g.Cin, g.Cout, g.M);
   const int nchunks = (int)cdiv(g.M, chunk_len);
   g.chunk_len = chunk_len;
   g.ci_tiles = ci_tiles;
@@ -374,31 +457,17 @@ torch::Tensor wgrad_bf16_fast(torch::Tensor x, torch::Tensor dy, int64_t KH,
 
   dim3 grid(ci_tiles, co_tiles, taps * nchunks);
   auto s = at::cuda::getCurrentCUDAStream();
-  const bool aligned = (g.Cin % 8 == 0) && (g.Cout % 8 == 0);
-
-  bool use_tr = false;
-  if (variant == "tr") {
-    TORCH_CHECK(aligned, "wgrad_bf16_fast: variant 'tr' needs Cin % 8 == 0 "
-                "and Cout % 8 == 0");
-    use_tr = true;
-  } else if (variant.empty()) {
-    use_tr = wgrad_default_is_tr(g.Cin, g.Cout, g.M);
-  } else {
-    TORCH_CHECK(variant == "regt", "wgrad_bf16_fast: unknown variant '",
-                variant, "'");
-  }
   const bool same = stride == 1 && g.Ho == g.H && g.Wo == g.W;
   auto* px = reinterpret_cast<const bf16*>(xc.data_ptr());
   auto* pdy = reinterpret_cast<const bf16*>(dyc.data_ptr());
 #define RTHD_WG_LAUNCH(A_, S_)                                           \
   hipLaunchKernelGGL((wgrad_bf16_kernel<A_, S_>), grid, dim3(256), 0, s, \
       px, pdy, dwp.data_ptr<float>(), g)
-  if (use_tr) {
-    WtrGeo tg;
-    tg.B = g.B; tg.H = g.H; tg.W = g.W; tg.Cin = g.Cin;
-    tg.Ho = g.Ho; tg.Wo = g.Wo; tg.Cout = g.Cout;
-    tg.KH = g.KH; tg.KW = g.KW; tg.stride = g.stride; tg.pad = g.pad;
-    tg.M = g.M; tg.chunk_len = g.chunk_len;
+  tg.chunk_len = g.chunk_len;
+  if (use_row) {
+    wgrad_row_launch(tg, nchunks, px, pdy, zero_page_bf16(xc),
+                     dwp.data_ptr<float>(), s);
+  } else if (use_tr) {
     wgrad_tr_launch(tg, nchunks, px, pdy, zero_page_bf16(xc),
                     dwp.data_ptr<float>(), s);
   }

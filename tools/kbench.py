@@ -1,7 +1,7 @@
 """Micro-benchmark individual HIP kernels (A/B timing + rocprof target).
 
 python tools/kbench.py [wgrad|conv|stem_wgrad|bn|nms|decode|all] [--iters N]
-    [--variant tr|regt]   (wgrad only)
+    [--variant row|tr|regt]   (wgrad only)
 Prints per-kernel ms and effective TFLOP/s on the flagship shapes; ``nms``
 prints the hard/soft batched NMS kernels against their eager twins,
 ``decode`` the logits-in decode against the composition it replaces.
@@ -51,9 +51,13 @@ def bench_wgrad(iters, variant=''):
         ('3x3 128ch @32^2 B16', 16, 128, 128, 32, 3, 1, 1),
         ('3x3 128ch @16^2 B16', 16, 128, 128, 16, 3, 1, 1),
         ('3x3 128ch @8^2 B16', 16, 128, 128, 8, 3, 1, 1),
+        ('3x3 128ch @256^2 B16', 16, 128, 128, 256, 3, 1, 1),
     ]
     print(f'wgrad variant: {variant or "default dispatch"}')
     for name, B, cin, cout, hw, k, stride, pad in shapes:
+        if variant == 'row' and not (k == 3 and stride == 1 and pad == 1
+                                     and hw % 32 == 0):
+            continue   # the tap-row kernel computes 3x3 s1 p1 only
         x = torch.randn(B, cin, hw, hw, device='cuda',
                         dtype=torch.bfloat16).contiguous(memory_format=CL)
         dy = torch.randn(B, cout, hw, hw, device='cuda',
@@ -306,9 +310,9 @@ if __name__ == '__main__':
     ap.add_argument('which', nargs='?', default='all')
     ap.add_argument('--iters', type=int, default=30)
     ap.add_argument('--variant', default='',
-                    choices=['', 'tr', 'regt'],
-                    help='wgrad kernel: tr = transposed-read, regt = '
-                         'register-transpose; default = the host dispatch '
+                    choices=['', 'row', 'tr', 'regt'],
+                    help='wgrad kernel: row = tap-row, tr = transposed-read, '
+                         'regt = register-transpose; default = the host dispatch '
                          'rule')
     args = ap.parse_args()
     torch.manual_seed(0)
