@@ -69,6 +69,19 @@ torch::Tensor conv_fwd_fp8r(torch::Tensor x, torch::Tensor wpk,
                             int64_t KH, int64_t KW, int64_t stride,
                             int64_t pad, int64_t Cout, int64_t act,
                             bool out_fp8);
+torch::Tensor conv_fwd_fp8r_tile128(torch::Tensor x, torch::Tensor wpk,
+                                    torch::Tensor scale, torch::Tensor shift,
+                                    c10::optional<torch::Tensor> skip,
+                                    int64_t KH, int64_t KW, int64_t stride,
+                                    int64_t pad, int64_t Cout, int64_t act,
+                                    bool out_fp8);
+torch::Tensor conv_fwd_fp8r_halo(torch::Tensor x, torch::Tensor wpk,
+                                 torch::Tensor scale, torch::Tensor shift,
+                                 c10::optional<torch::Tensor> skip,
+                                 int64_t KH, int64_t KW, int64_t stride,
+                                 int64_t pad, int64_t Cout, int64_t act,
+                                 bool out_fp8);
+int64_t fp8_halo_launch_count();
 torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wpk,
                        torch::Tensor scale, torch::Tensor shift,
                        c10::optional<torch::Tensor> skip,
@@ -164,6 +177,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pack_weights_pair", &rthd::pack_weights_pair);
   m.def("pack_weights_fp8", &rthd::pack_weights_fp8);
   m.def("conv_fwd_fp8r", &rthd::conv_fwd_fp8r);
+  m.def("conv_fwd_fp8r_tile128", &rthd::conv_fwd_fp8r_tile128);
+  m.def("conv_fwd_fp8r_halo", &rthd::conv_fwd_fp8r_halo);
+  m.def("fp8_halo_launch_count", &rthd::fp8_halo_launch_count);
   m.def("conv_fwd", &rthd::conv_fwd);
   m.def("conv_fwd_small", &rthd::conv_fwd_small);
   m.def("conv_fwd_k64", &rthd::conv_fwd_k64);

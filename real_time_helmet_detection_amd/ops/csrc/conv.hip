@@ -512,38 +512,6 @@ uint64_t conv_key(const ConvGeo& g) {
   return h;
 }
 
-bool stream_capturing(hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-    (void)hipGetLastError();
-    return true;  // be conservative: never time inside a capture
-  }
-  return st != hipStreamCaptureStatusNone;
-}
-
-// min-of-3 time of fn() in usec on stream s after one warm run (fn must
-// enqueue its work on s); synchronizes the stream
-template <typename F>
-float time_usec(F&& fn, hipStream_t s) {
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  fn();  // warm (code paths, allocator)
-  float best = 1e30f;
-  for (int r = 0; r < 3; ++r) {
-    (void)hipEventRecord(e0, s);
-    fn();
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    best = std::min(best, ms * 1000.f);
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return best;
-}
-
 // 128x128/K32 bf16 kernel on prepared operands; p1/p2 (both or neither,
 // no skip) select the fused-stats epilogue
 void launch_big(const ConvGeo& g, const ConvOperands& o, int act,

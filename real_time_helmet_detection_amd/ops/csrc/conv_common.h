@@ -1,5 +1,6 @@
 // Shared pieces of the MFMA implicit-GEMM conv family (conv.hip,
-// conv_k64.hip, conv_small.hip, conv_fp8.hip): geometry, LDS swizzles, the
+// conv_k64.hip, conv_small.hip, conv_halo.hip, conv_fp8.hip,
+// conv_halo_fp8.hip): geometry, LDS swizzles, the
 // fused epilogue, the 128-B-row double-buffered main loop, the host operand
 // preparation and the cross-file host prototypes. Each kernel file keeps
 // its tile shape, its fragment reads and its MFMA calls.
@@ -7,6 +8,8 @@
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+
+#include <algorithm>
 
 #include "common.h"
 
@@ -280,6 +283,41 @@ inline T* conv_ptr(const torch::Tensor& t) {
 // per-device cached 16-B zero page (conv.hip)
 const bf16* zero_page_bf16(const torch::Tensor& like);
 
+// ---- first-sight measurement of kernel variants (conv.hip, conv_fp8.hip)
+// no timing API is legal inside a stream capture: a capturing stream takes
+// the caller's heuristic instead
+inline bool stream_capturing(hipStream_t s) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    return true;  // be conservative: never time inside a capture
+  }
+  return st != hipStreamCaptureStatusNone;
+}
+
+// min-of-3 time of fn() in usec on stream s after one warm run (fn must
+// enqueue its work on s); synchronizes the stream
+template <typename F>
+float time_usec(F&& fn, hipStream_t s) {
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0);
+  (void)hipEventCreate(&e1);
+  fn();  // warm (code paths, allocator)
+  float best = 1e30f;
+  for (int r = 0; r < 3; ++r) {
+    (void)hipEventRecord(e0, s);
+    fn();
+    (void)hipEventRecord(e1, s);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    best = std::min(best, ms * 1000.f);
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return best;
+}
+
 // variant launchers on prepared bf16 operands: write o.y on the current
 // stream. p1/p2 (both or neither; no skip) select the fused-stats epilogue.
 void launch_k64(const ConvGeo& g, const ConvOperands& o, int act,
@@ -289,6 +327,10 @@ void launch_small(const ConvGeo& g, const ConvOperands& o, int act,
 // halo-tile 3x3 variant: the shapes it takes, and its launcher (no stats)
 bool halo_eligible(const ConvGeo& g);                       // conv_halo.hip
 void launch_halo(const ConvGeo& g, const ConvOperands& o, int act);
+// halo-tile fp8 3x3 variant on prepared e4m3 operands  (conv_halo_fp8.hip)
+bool fp8_halo_eligible(const ConvGeo& g);
+void launch_halo_fp8(const ConvGeo& g, const ConvOperands& o, int act,
+                     bool out_fp8);
 
 // python-visible entry points
 torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16);
@@ -327,5 +369,20 @@ torch::Tensor conv_fwd_fp8r(torch::Tensor x, torch::Tensor wpk,
                             int64_t KH, int64_t KW, int64_t stride,
                             int64_t pad, int64_t Cout, int64_t act,
                             bool out_fp8);
+// the two kernels conv_fwd_fp8r chooses between, explicitly
+torch::Tensor conv_fwd_fp8r_tile128(torch::Tensor x, torch::Tensor wpk,
+                                    torch::Tensor scale, torch::Tensor shift,
+                                    c10::optional<torch::Tensor> skip,
+                                    int64_t KH, int64_t KW, int64_t stride,
+                                    int64_t pad, int64_t Cout, int64_t act,
+                                    bool out_fp8);
+torch::Tensor conv_fwd_fp8r_halo(torch::Tensor x, torch::Tensor wpk,
+                                 torch::Tensor scale, torch::Tensor shift,
+                                 c10::optional<torch::Tensor> skip,
+                                 int64_t KH, int64_t KW, int64_t stride,
+                                 int64_t pad, int64_t Cout, int64_t act,
+                                 bool out_fp8);
+// halo-tile fp8 launches of this process so far (host-side counter)
+int64_t fp8_halo_launch_count();
 
 }  // namespace rthd

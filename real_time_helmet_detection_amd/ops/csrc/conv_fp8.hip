@@ -18,6 +18,10 @@
 // glds per step, source chunk pre-swizzled (chunk ^ (row&7)) so the
 // lane-linear glds image matches the conflict-reduced fragment reads
 // (staging loop: conv_mainloop_row128 in conv_common.h).
+#include <cstdlib>
+#include <mutex>
+#include <unordered_map>
+
 #include "conv_common.h"
 
 namespace rthd {
@@ -79,27 +83,37 @@ void conv_fwd_fp8r_kernel(const fp8e4* __restrict__ x,
       g.M, g.Cout, scale, shift, skip, y, act, nullptr, nullptr, 0);
 }
 
-// x: e4m3 channels_last; wpk from pack_weights_fp8 (per-cout pre-scaled,
-// K padded to 128); out_fp8 selects e4m3 (mid-network) vs bf16 (heads).
-torch::Tensor conv_fwd_fp8r(torch::Tensor x, torch::Tensor wpk,
-                            torch::Tensor scale, torch::Tensor shift,
-                            c10::optional<torch::Tensor> skip,
-                            int64_t KH, int64_t KW, int64_t stride,
-                            int64_t pad, int64_t Cout, int64_t act,
-                            bool out_fp8) {
+namespace {
+
+// dtype checks, geometry and operands shared by the three entry points
+ConvGeo fp8r_geo(const char* op, const torch::Tensor& x,
+                 const torch::Tensor& wpk,
+                 const c10::optional<torch::Tensor>& skip, int64_t KH,
+                 int64_t KW, int64_t stride, int64_t pad, int64_t Cout) {
   TORCH_CHECK(x.scalar_type() == at::kFloat8_e4m3fn,
-              "conv_fwd_fp8r: x must be e4m3 (fp8-resident chain)");
+              op, ": x must be e4m3 (fp8-resident chain)");
   TORCH_CHECK(wpk.scalar_type() == at::kFloat8_e4m3fn,
-              "conv_fwd_fp8r: packed weight shape");
+              op, ": packed weight shape");
   TORCH_CHECK(!skip.has_value() ||
               skip->scalar_type() == at::kFloat8_e4m3fn,
-              "conv_fwd_fp8r: skip must be e4m3");
-  const ConvGeo g = make_conv_geo("conv_fwd_fp8r", x, wpk, KH, KW, stride,
-                                  pad, Cout, 128);
-  auto o = prep_conv_operands(
+              op, ": skip must be e4m3");
+  return make_conv_geo(op, x, wpk, KH, KW, stride, pad, Cout, 128);
+}
+
+ConvOperands fp8r_operands(const ConvGeo& g, const torch::Tensor& x,
+                           const torch::Tensor& wpk,
+                           const torch::Tensor& scale,
+                           const torch::Tensor& shift,
+                           const c10::optional<torch::Tensor>& skip,
+                           bool out_fp8) {
+  return prep_conv_operands(
       g, x, wpk, scale, shift, skip, at::kFloat8_e4m3fn,
       out_fp8 ? at::kFloat8_e4m3fn : at::kBFloat16);
+}
 
+// the per-tap 128x128 tile kernel of this file on prepared operands
+void launch_fp8_tile128(const ConvGeo& g, const ConvOperands& o, int act,
+                        bool out_fp8) {
   dim3 grid(cdiv(g.M, 128), g.Coutp / 128);
   auto s = at::cuda::getCurrentCUDAStream();
 #define RTHD_F8_LAUNCH(SKIP_, OUT_T)                                      \
@@ -118,6 +132,104 @@ torch::Tensor conv_fwd_fp8r(torch::Tensor x, torch::Tensor wpk,
   }
 #undef RTHD_F8_LAUNCH
   HIP_CHECK_LAST();
+}
+
+// ---- per-shape choice between the tile128 and the halo-tile kernel. Both
+// give the same bits, so the choice only decides the time. An eligible
+// shape is measured on first sight (the time_usec pattern of
+// choose_conv_variant) and the winner cached; under stream capture or
+// RTHD_NO_AUTOTUNE the block-count heuristic decides.
+std::mutex g_fp8_tune_mu;
+std::unordered_map<uint64_t, bool> g_fp8_tune;
+
+// smallest block count (B * H/8 * W/16 * Coutp/128) from which the halo
+// kernel is ahead in every pair of the kbench table
+// (profiles/conv_fp8_halo.md)
+constexpr int64_t FP8_HALO_MIN_BLOCKS = 128;
+
+bool fp8_halo_heuristic(const ConvGeo& g) {
+  return (int64_t)cdiv(g.M, 128) * (g.Coutp / 128) >= FP8_HALO_MIN_BLOCKS;
+}
+
+bool choose_fp8_halo(const ConvGeo& g, const ConvOperands& o, int act,
+                     bool out_fp8) {
+  uint64_t key = 1469598103934665603ull;
+  auto mix = [&key](uint64_t v) {
+    key ^= v + 0x9e3779b97f4a7c15ull + (key << 6) + (key >> 2);
+  };
+  mix(g.B); mix(g.H); mix(g.W); mix(g.Cout); mix(o.skip.defined());
+  mix(out_fp8);
+  // RTHD_NO_AUTOTUNE is read per call and asks for the heuristic whatever
+  // an earlier call measured: it neither reads nor fills the cache
+  if (getenv("RTHD_NO_AUTOTUNE")) return fp8_halo_heuristic(g);
+  {
+    std::lock_guard<std::mutex> lk(g_fp8_tune_mu);
+    auto it = g_fp8_tune.find(key);
+    if (it != g_fp8_tune.end()) return it->second;
+  }
+  auto s = at::cuda::getCurrentCUDAStream();
+  // a capture sees the measured choice of the eager warm-up if there was
+  // one, else the heuristic; an unmeasured shape stays unmeasured
+  if (stream_capturing(s)) return fp8_halo_heuristic(g);
+  const float tt = time_usec(
+      [&] { launch_fp8_tile128(g, o, act, out_fp8); }, s.stream());
+  const float th = time_usec(
+      [&] { launch_halo_fp8(g, o, act, out_fp8); }, s.stream());
+  const bool halo = th < tt;
+  std::lock_guard<std::mutex> lk(g_fp8_tune_mu);
+  g_fp8_tune[key] = halo;
+  return halo;
+}
+
+}  // namespace
+
+// x: e4m3 channels_last; wpk from pack_weights_fp8 (per-cout pre-scaled,
+// K padded to 128); out_fp8 selects e4m3 (mid-network) vs bf16 (heads).
+// Runs the halo-tile kernel (conv_halo_fp8.hip) where the shape is eligible
+// and it is the faster one, else the 128x128 tile kernel; RTHD_FP8_HALO=0
+// forces the latter.
+torch::Tensor conv_fwd_fp8r(torch::Tensor x, torch::Tensor wpk,
+                            torch::Tensor scale, torch::Tensor shift,
+                            c10::optional<torch::Tensor> skip,
+                            int64_t KH, int64_t KW, int64_t stride,
+                            int64_t pad, int64_t Cout, int64_t act,
+                            bool out_fp8) {
+  const ConvGeo g = fp8r_geo("conv_fwd_fp8r", x, wpk, skip, KH, KW, stride,
+                             pad, Cout);
+  auto o = fp8r_operands(g, x, wpk, scale, shift, skip, out_fp8);
+  const char* env = getenv("RTHD_FP8_HALO");
+  const bool off = env && env[0] == '0' && env[1] == '\0';
+  if (!off && fp8_halo_eligible(g) &&
+      choose_fp8_halo(g, o, (int)act, out_fp8))
+    launch_halo_fp8(g, o, (int)act, out_fp8);
+  else
+    launch_fp8_tile128(g, o, (int)act, out_fp8);
+  return o.y;
+}
+
+torch::Tensor conv_fwd_fp8r_tile128(torch::Tensor x, torch::Tensor wpk,
+                                    torch::Tensor scale, torch::Tensor shift,
+                                    c10::optional<torch::Tensor> skip,
+                                    int64_t KH, int64_t KW, int64_t stride,
+                                    int64_t pad, int64_t Cout, int64_t act,
+                                    bool out_fp8) {
+  const ConvGeo g = fp8r_geo("conv_fwd_fp8r_tile128", x, wpk, skip, KH, KW,
+                             stride, pad, Cout);
+  auto o = fp8r_operands(g, x, wpk, scale, shift, skip, out_fp8);
+  launch_fp8_tile128(g, o, (int)act, out_fp8);
+  return o.y;
+}
+
+torch::Tensor conv_fwd_fp8r_halo(torch::Tensor x, torch::Tensor wpk,
+                                 torch::Tensor scale, torch::Tensor shift,
+                                 c10::optional<torch::Tensor> skip,
+                                 int64_t KH, int64_t KW, int64_t stride,
+                                 int64_t pad, int64_t Cout, int64_t act,
+                                 bool out_fp8) {
+  const ConvGeo g = fp8r_geo("conv_fwd_fp8r_halo", x, wpk, skip, KH, KW,
+                             stride, pad, Cout);
+  auto o = fp8r_operands(g, x, wpk, scale, shift, skip, out_fp8);
+  launch_halo_fp8(g, o, (int)act, out_fp8);
   return o.y;
 }
 

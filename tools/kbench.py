@@ -129,6 +129,10 @@ def bench_fp8(iters):
     shapes = [
         ('3x3 128ch @128^2 B8', 8, 128, 128, 128, 3, 1, 1),
         ('3x3 128ch @256^2 B8', 8, 128, 128, 256, 3, 1, 1),
+        # the smallest routed shapes of the b8 and b4 serving steps
+        # (M = 32768 and 16384: 256 and 128 blocks)
+        ('3x3 128ch @64^2 B8', 8, 128, 128, 64, 3, 1, 1),
+        ('3x3 128ch @64^2 B4', 4, 128, 128, 64, 3, 1, 1),
         ('3x3 64->128 @256^2 B8', 8, 64, 128, 256, 3, 1, 1),
         ('1x1 128ch @128^2 B8', 8, 128, 128, 128, 1, 1, 0),
     ]
@@ -143,8 +147,23 @@ def bench_fp8(iters):
         ms = timeit(lambda: C.conv_fwd_fp8r(x8, wpk8, ones, zeros, None,
                                             k, k, stride, pad, cout, 1,
                                             True), iters)
-        print(f'conv(fp8 K128) {name:24s} {ms*1e3:8.1f}us  '
+        print(f'conv(fp8 auto) {name:24s} {ms*1e3:8.1f}us  '
               f'{fl/ms/1e9:7.1f} TF')
+        if k == 3 and cin == 128:
+            # the two kernels conv_fwd_fp8r chooses between: three
+            # back-to-back pairs, without and with the e4m3 skip input
+            sk8 = (torch.randn(B, cout, hw, hw, device='cuda') * 0.5) \
+                .to(torch.float8_e4m3fn).contiguous(memory_format=CL)
+            for tag, skip in (('', None), ('+skip', sk8)):
+                for _ in range(3):
+                    for kind, fn in (('tile128', C.conv_fwd_fp8r_tile128),
+                                     ('halo', C.conv_fwd_fp8r_halo)):
+                        ms = timeit(lambda: fn(x8, wpk8, ones, zeros, skip,
+                                               k, k, stride, pad, cout, 1,
+                                               True), iters)
+                        label = f'conv(fp8 {kind}{tag})'
+                        print(f'{label:24s} {name:22s} {ms*1e3:8.1f}us  '
+                              f'{fl/ms/1e9:7.1f} TF')
         # bf16 twin on the same shape for the A/B
         xb = torch.randn(B, cin, hw, hw, device='cuda',
                          dtype=torch.bfloat16).contiguous(memory_format=CL)
