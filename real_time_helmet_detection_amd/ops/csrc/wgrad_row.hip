@@ -24,38 +24,18 @@
 //   issue different numbers of X pieces (9 pieces over 4 waves), so each
 //   wave's vmcnt count is its own, picked by a wave-uniform branch.
 // The geometry lives in wgrad_row_geo.h (on top of wgrad_tr_geo.h) and is
-// walked on the host by tests/test_wgrad_row_geo.py.
-//
-// AUDIT ON EVERY EDIT of this file or of the toolchain (the rule of
-// wgrad_tr.hip): in the .s of wgrad_row_kernel, between the first
-// ds_read_b64_tr_b16 of the loop and the lgkmcnt wait that covers it,
-// nothing touches a read's destination: no v_mov, no v_accvgpr copy, no
-// scratch; ScratchSize is 0. Resource usage of the kept instantiation is
-// recorded in profiles/wgrad_row.md.
-#include <mutex>
-
-#include "conv_common.h"
+// walked on the host by tests/test_geo_checks.py. Resource usage of the kept
+// instantiation is recorded in profiles/wgrad_row.md.
+#include "lds_async.h"
 #include "wgrad_row_geo.h"
 
 namespace rthd {
 
 namespace {
 
-using i16x4 = __attribute__((ext_vector_type(4))) short;
 using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
-typedef __attribute__((address_space(3))) char lds_char;
 
 constexpr int WROW_NBUF = 3;   // LDS ring depth
-constexpr int WROW_NUM_XCD = 8;
-
-// one transposed read of the main loop (see tr_read in wgrad_tr.hip)
-template <int OFF>
-DEV_INLINE i16x4 row_tr_read(uint32_t addr) {
-  i16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
-               : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
 
 // zero the edge element of a fragment half: `word` is all ones in the
 // lanes and k-blocks that hold no edge
@@ -66,6 +46,8 @@ DEV_INLINE i16x4 row_mask(i16x4 v, uint32_t word) {
   return __builtin_bit_cast(i16x4, u);
 }
 
+// wgrad_row_kernel reads its fragments with lds_read_tr16_b64 and waits of
+// its own: the audit rule of lds_async.h applies to every edit.
 template <int BM, int BN>
 __global__ __launch_bounds__(256, 2)
 void wgrad_row_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
@@ -86,15 +68,12 @@ void wgrad_row_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   // One block per (kernel row, px-chunk, ci-tile, co-tile) cell, chunk-
-  // major, with the XCD cell remap of wgrad_tr.hip: the rows x tiles blocks
+  // major, with xcd_cell_remap (wgrad_tr_geo.h): the rows x tiles blocks
   // that share a px chunk get consecutive cells, and one XCD takes a
   // contiguous cell range. Speed only.
   const int ci_t = (g.Cin + BM - 1) / BM, co_t = (g.Cout + BN - 1) / BN;
   int cell = blockIdx.x;
-  if (xcd_remap) {
-    const int G = gridDim.x, k = cell % WROW_NUM_XCD, j = cell / WROW_NUM_XCD;
-    cell = k * (G / WROW_NUM_XCD) + min(k, G % WROW_NUM_XCD) + j;
-  }
+  if (xcd_remap) cell = xcd_cell_remap(cell, gridDim.x);
   const int z = cell / (ci_t * co_t);
   const int ty = z % 3;
   const int chunk = z / 3;
@@ -159,7 +138,7 @@ void wgrad_row_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
 
   // fragment read addresses of k-block 0 in ring buffer 0 (k-block 1 is 32
   // rows further: an offset immediate; the swizzle has period 16 rows)
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char*)smem;
+  const uint32_t lds0 = lds_base(smem);
   uint32_t aoff[3][MI][2], boff[NI][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -188,11 +167,11 @@ void wgrad_row_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
     // this wave's loads of `step` have landed (all but the newest step's)
     if (step + 1 < nsteps) {
       if (nxw == NXMAX)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NXMAX + NY) : "memory");
+        wait_vm<NXMAX + NY>();
       else
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NXMIN + NY) : "memory");
+        wait_vm<NXMIN + NY>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
     }
     // ... and everyone's; every wave is also done reading step-1's buffer,
     // which the loads issued below overwrite
@@ -204,30 +183,29 @@ void wgrad_row_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
     for (int t = 0; t < 3; ++t)
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
-        xlo[0][t][mi] = row_tr_read<0>(aoff[t][mi][0] + boffs);
-        xhi[0][t][mi] = row_tr_read<0>(aoff[t][mi][1] + boffs);
+        xlo[0][t][mi] = lds_read_tr16_b64<0>(aoff[t][mi][0] + boffs);
+        xhi[0][t][mi] = lds_read_tr16_b64<0>(aoff[t][mi][1] + boffs);
       }
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      ylo[0][ni] = row_tr_read<0>(boff[ni][0] + boffs);
-      yhi[0][ni] = row_tr_read<0>(boff[ni][1] + boffs);
+      ylo[0][ni] = lds_read_tr16_b64<0>(boff[ni][0] + boffs);
+      yhi[0][ni] = lds_read_tr16_b64<0>(boff[ni][1] + boffs);
     }
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) {
-        xlo[1][t][mi] = row_tr_read<32 * BM * 2>(aoff[t][mi][0] + boffs);
-        xhi[1][t][mi] = row_tr_read<32 * BM * 2>(aoff[t][mi][1] + boffs);
+        xlo[1][t][mi] = lds_read_tr16_b64<32 * BM * 2>(aoff[t][mi][0] + boffs);
+        xhi[1][t][mi] = lds_read_tr16_b64<32 * BM * 2>(aoff[t][mi][1] + boffs);
       }
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      ylo[1][ni] = row_tr_read<32 * BN * 2>(boff[ni][0] + boffs);
-      yhi[1][ni] = row_tr_read<32 * BN * 2>(boff[ni][1] + boffs);
+      ylo[1][ni] = lds_read_tr16_b64<32 * BN * 2>(boff[ni][0] + boffs);
+      yhi[1][ni] = lds_read_tr16_b64<32 * BN * 2>(boff[ni][1] + boffs);
     }
 
-    const int wbuf = rbuf == 0 ? 2 : rbuf - 1;
-    if (step + 2 < nsteps) issue_step(step + 2, wbuf);
-    rbuf = rbuf == 2 ? 0 : rbuf + 1;
+    if (step + 2 < nsteps) issue_step(step + 2, ring3_prev(rbuf));
+    rbuf = ring3_next(rbuf);
 
     // edge masks of the two k-blocks (wave-uniform selects)
     uint32_t mlo[KS], mhi[KS];
@@ -248,20 +226,17 @@ void wgrad_row_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
       // LDS returns in order: k-block 0 is complete once at most 15 of the
       // RD1 >= 15 reads of k-block 1 are outstanding (the counter's range)
       static_assert(RD1 >= 15, "lgkmcnt(15) must cover k-block 0");
-      if (ks == 0)
-        asm volatile("s_waitcnt lgkmcnt(15)");
-      else
-        asm volatile("s_waitcnt lgkmcnt(0)");
+      wait_lgkm(ks == 0 ? 15 : 0);
       // the asm reads are invisible to the compiler's own wait insertion:
       // tie every fragment register to a point after the wait above
 #pragma unroll
       for (int t = 0; t < 3; ++t)
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
-          asm volatile("" : "+v"(xlo[ks][t][mi]), "+v"(xhi[ks][t][mi]));
+          frag_ready(xlo[ks][t][mi], xhi[ks][t][mi]);
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        asm volatile("" : "+v"(ylo[ks][ni]), "+v"(yhi[ks][ni]));
+        frag_ready(ylo[ks][ni], yhi[ks][ni]);
       __builtin_amdgcn_sched_barrier(0);
       bf16x8 yb[NI];
 #pragma unroll
@@ -321,25 +296,9 @@ void row_launch_tile(const WtrGeo& g, int nchunks, const bf16* x,
   // The XCD cell remap was re-measured for this kernel: even at 32^2 and
   // 64^2 (+-2 us), -3 % at 128^2, -9 % at 256^2 (profiles/wgrad_row.md)
   const int remap = g.M >= 65536;
-  // 3 ring buffers, above the 64 KB a kernel gets without opting in
-  const size_t lds =
-      (size_t)WROW_NBUF * (wrow_x_pieces(BM) * 1024 + WTR_KB * BN * 2);
-  {
-    static std::mutex mu;
-    static uint64_t done = 0;   // one bit per device
-    int dev = 0;
-    TORCH_CHECK(hipGetDevice(&dev) == hipSuccess && dev < 64,
-                "wgrad_row: bad device");
-    std::lock_guard<std::mutex> lk(mu);
-    if (!((done >> dev) & 1)) {
-      const hipError_t e = hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&wgrad_row_kernel<BM, BN>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      TORCH_CHECK(e == hipSuccess, "wgrad_row: cannot opt in to ", lds,
-                  " B of LDS: ", hipGetErrorString(e));
-      done |= (uint64_t)1 << dev;
-    }
-  }
+  // 3 ring buffers
+  const int lds = WROW_NBUF * (wrow_x_pieces(BM) * 1024 + WTR_KB * BN * 2);
+  lds_opt_in<&wgrad_row_kernel<BM, BN>>(lds, "wgrad_row");
   hipLaunchKernelGGL((wgrad_row_kernel<BM, BN>), grid, dim3(256), lds, s, x,
                      dy, zpage, dwp, g, remap);
 }

@@ -23,51 +23,21 @@
 //   reduce are those of wgrad_fast.hip: with equal chunk length the result
 //   is bitwise equal to that kernel.
 // The LDS layout, lane maps and source map live in wgrad_tr_geo.h and are
-// walked on the host by tests/test_wgrad_tr_geo.py.
-#include <mutex>
-
-#include "conv_common.h"
+// walked on the host by tests/test_geo_checks.py.
+#include "lds_async.h"
 #include "wgrad_tr_geo.h"
 
 namespace rthd {
 
 namespace {
 
-using i16x4 = __attribute__((ext_vector_type(4))) short;
 typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
 
-typedef __attribute__((address_space(3))) char lds_char;
-
 constexpr int WTR_NBUF = 3;   // LDS ring depth
-constexpr int WTR_NUM_XCD = 8;
-
-// One transposed read in the main loop, as inline asm. Through the builtin
-// the compiler orders every LDS read behind ALL pending global_load_lds
-// with s_waitcnt vmcnt(0) (it cannot see that ring buffers are disjoint),
-// which forbids loads in flight across a K-step. The kernel places the
-// vmcnt / lgkmcnt waits for these reads itself.
-//
-// The compiler takes the "=v" result as written when the asm ends, while
-// the data lands only at the kernel's lgkmcnt wait. So between a read and
-// its wait the compiler must emit nothing that touches the result: no
-// v_mov, no v_accvgpr copy, no scratch spill. AUDIT ON EVERY EDIT of this
-// file or of the toolchain: in the .s of wgrad_tr_kernel, the lines from
-// the first ds_read_b64_tr_b16 of the loop to `s_waitcnt lgkmcnt(0)` hold
-// only the reads, address arithmetic on OTHER registers, global_load_lds
-// and MFMAs; ScratchSize is 0. Checked for this version (101 VGPR + 32
-// AGPR). tests/test_gpu_wgrad_tr.py runs many K-steps per chunk bitwise
-// against the register-transpose kernel and fails on such a regression.
-template <int OFF>
-DEV_INLINE i16x4 tr_read(uint32_t addr) {
-  i16x4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
-               : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
 
 // the two transposed reads of one 16x16x32 operand, k-slots 0..3 and 4..7,
 // through the compiler builtin (the self-test; the main loop issues the
-// same instruction through tr_read)
+// same instruction through lds_read_tr16_b64)
 DEV_INLINE bf16x8 tr_read_frag(const char* p0, const char* p1) {
   const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)p0);
   const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)p1);
@@ -93,6 +63,8 @@ void lds_tr16_selftest_kernel(short* __restrict__ out) {
   }
 }
 
+// wgrad_tr_kernel reads its fragments with lds_read_tr16_b64 and waits of
+// its own: the audit rule of lds_async.h applies to every edit.
 template <int BM, int BN>
 __global__ __launch_bounds__(256)
 void wgrad_tr_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
@@ -111,20 +83,15 @@ void wgrad_tr_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
 
   // One block per (tap, px-chunk, ci-tile, co-tile) cell, chunk-major: the
   // taps x tiles blocks that share one px chunk's X/dY data have
-  // consecutive cell ids. Blocks are dealt round-robin over the 8 XCDs
-  // (block b and b+8 share one), so with cell = block id those blocks land
-  // on all 8 XCDs and every XCD's L2 streams every chunk: 8x the unique
-  // bytes over the fabric, which is what bounded the kernel (the loads ran
-  // at Infinity-Cache bandwidth). xcd_remap gives the blocks of one XCD a
-  // contiguous range of cells instead, so a chunk is fetched by one L2.
-  // Speed only: any placement computes the same bits.
+  // consecutive cell ids. With cell = block id those blocks land on all 8
+  // XCDs and every XCD's L2 streams every chunk: 8x the unique bytes over
+  // the fabric, which is what bounded the kernel (the loads ran at
+  // Infinity-Cache bandwidth). With xcd_cell_remap (wgrad_tr_geo.h) a chunk
+  // is fetched by one L2. Speed only: any placement computes the same bits.
   const int taps = g.KH * g.KW;
   const int ci_t = (g.Cin + BM - 1) / BM, co_t = (g.Cout + BN - 1) / BN;
   int cell = blockIdx.x;
-  if (xcd_remap) {
-    const int G = gridDim.x, k = cell % WTR_NUM_XCD, j = cell / WTR_NUM_XCD;
-    cell = k * (G / WTR_NUM_XCD) + min(k, G % WTR_NUM_XCD) + j;
-  }
+  if (xcd_remap) cell = xcd_cell_remap(cell, gridDim.x);
   const int z = cell / (ci_t * co_t);
   const int t = z % taps;
   const int chunk = z / taps;
@@ -187,7 +154,7 @@ void wgrad_tr_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
 
   // fragment read addresses of k-block 0 in ring buffer 0 (k-block 1 is 32
   // rows further: an offset immediate)
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_char*)smem;
+  const uint32_t lds0 = lds_base(smem);
   uint32_t aoff[MI][2], boff[NI][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -211,9 +178,9 @@ void wgrad_tr_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
   for (int step = 0; step < nsteps; ++step) {
     // this wave's loads of `step` have landed (all but the newest step's)
     if (step + 1 < nsteps)
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NX + NY) : "memory");
+      wait_vm<NX + NY>();
     else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
     // ... and everyone's; every wave is also done reading step-1's buffer,
     // which the loads issued below overwrite
     __builtin_amdgcn_s_barrier();
@@ -222,28 +189,27 @@ void wgrad_tr_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
     i16x4 xlo[KS][MI], xhi[KS][MI], ylo[KS][NI], yhi[KS][NI];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      xlo[0][mi] = tr_read<0>(aoff[mi][0] + boffs);
-      xhi[0][mi] = tr_read<0>(aoff[mi][1] + boffs);
+      xlo[0][mi] = lds_read_tr16_b64<0>(aoff[mi][0] + boffs);
+      xhi[0][mi] = lds_read_tr16_b64<0>(aoff[mi][1] + boffs);
     }
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      ylo[0][ni] = tr_read<0>(boff[ni][0] + boffs);
-      yhi[0][ni] = tr_read<0>(boff[ni][1] + boffs);
+      ylo[0][ni] = lds_read_tr16_b64<0>(boff[ni][0] + boffs);
+      yhi[0][ni] = lds_read_tr16_b64<0>(boff[ni][1] + boffs);
     }
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      xlo[1][mi] = tr_read<32 * BM * 2>(aoff[mi][0] + boffs);
-      xhi[1][mi] = tr_read<32 * BM * 2>(aoff[mi][1] + boffs);
+      xlo[1][mi] = lds_read_tr16_b64<32 * BM * 2>(aoff[mi][0] + boffs);
+      xhi[1][mi] = lds_read_tr16_b64<32 * BM * 2>(aoff[mi][1] + boffs);
     }
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
-      ylo[1][ni] = tr_read<32 * BN * 2>(boff[ni][0] + boffs);
-      yhi[1][ni] = tr_read<32 * BN * 2>(boff[ni][1] + boffs);
+      ylo[1][ni] = lds_read_tr16_b64<32 * BN * 2>(boff[ni][0] + boffs);
+      yhi[1][ni] = lds_read_tr16_b64<32 * BN * 2>(boff[ni][1] + boffs);
     }
 
-    const int wbuf = rbuf == 0 ? 2 : rbuf - 1;
-    if (step + 2 < nsteps) issue_step(step + 2, wbuf);
-    rbuf = rbuf == 2 ? 0 : rbuf + 1;
+    if (step + 2 < nsteps) issue_step(step + 2, ring3_prev(rbuf));
+    rbuf = ring3_next(rbuf);
 
     // raise issue priority for the MFMA run: co-resident waves still in
     // their address math yield issue slots to it
@@ -253,18 +219,15 @@ void wgrad_tr_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy,
     for (int ks = 0; ks < KS; ++ks) {
       // LDS returns in order: k-block 0 is complete once at most the
       // k-block 1 reads are outstanding (the counter saturates at 15)
-      if (ks == 0)
-        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(RD1 < 15 ? RD1 : 15));
-      else
-        asm volatile("s_waitcnt lgkmcnt(0)");
+      wait_lgkm(ks == 0 ? (RD1 < 15 ? RD1 : 15) : 0);
       // the asm reads are invisible to the compiler's own wait insertion:
       // tie every fragment register to a point after the wait above
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
-        asm volatile("" : "+v"(xlo[ks][mi]), "+v"(xhi[ks][mi]));
+        frag_ready(xlo[ks][mi], xhi[ks][mi]);
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
-        asm volatile("" : "+v"(ylo[ks][ni]), "+v"(yhi[ks][ni]));
+        frag_ready(ylo[ks][ni], yhi[ks][ni]);
       __builtin_amdgcn_sched_barrier(0);
       bf16x8 xa[MI], yb[NI];
 #pragma unroll
@@ -324,24 +287,9 @@ void wgrad_tr_launch(const WtrGeo& g, int nchunks, const bf16* x,
   // matter (measured: +4 us at 32^2, even at 64^2, -6..-37 % from 128^2
   // up).
   const int remap = g.M >= 65536;
-  // 3 ring buffers = 72 KB, above the 64 KB a kernel gets without opting in
-  const size_t lds = (size_t)WTR_NBUF * WTR_KB * (WTR_BM + WTR_BN) * 2;
-  {
-    static std::mutex mu;
-    static uint64_t done = 0;   // one bit per device
-    int dev = 0;
-    TORCH_CHECK(hipGetDevice(&dev) == hipSuccess && dev < 64,
-                "wgrad_tr: bad device");
-    std::lock_guard<std::mutex> lk(mu);
-    if (!((done >> dev) & 1)) {
-      const hipError_t e = hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&wgrad_tr_kernel<WTR_BM, WTR_BN>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      TORCH_CHECK(e == hipSuccess, "wgrad_tr: cannot opt in to ", lds,
-                  " B of LDS: ", hipGetErrorString(e));
-      done |= (uint64_t)1 << dev;
-    }
-  }
+  // 3 ring buffers = 72 KB
+  const int lds = WTR_NBUF * WTR_KB * (WTR_BM + WTR_BN) * 2;
+  lds_opt_in<&wgrad_tr_kernel<WTR_BM, WTR_BN>>(lds, "wgrad_tr");
   hipLaunchKernelGGL((wgrad_tr_kernel<WTR_BM, WTR_BN>), grid, dim3(256), lds,
                      s, x, dy, zpage, dwp, g, remap);
 }

@@ -40,6 +40,20 @@ WTR_HD int wtr_chunk_len(int M, int Cin, int Cout, int taps, int forced) {
   return len;
 }
 
+// ------------------------------ block -> cell -------------------------------
+// Blocks are dealt round-robin over the XCDs (block b and b + NUM_XCD share
+// one). The cells that share data are numbered consecutively, so with
+// cell = block id they land on all XCDs and every XCD's L2 streams all of
+// the data. The remap gives the blocks of XCD k a contiguous range of cells
+// instead (the first G % NUM_XCD XCDs take one cell more): a permutation of
+// 0 .. G - 1 for any grid size G. Speed only.
+constexpr int NUM_XCD = 8;
+
+WTR_HD int xcd_cell_remap(int cell, int G) {
+  const int k = cell % NUM_XCD, j = cell / NUM_XCD, rem = G % NUM_XCD;
+  return k * (G / NUM_XCD) + (k < rem ? k : rem) + j;
+}
+
 // ------------------------------ LDS image -----------------------------------
 // One operand tile is [WTR_KB px][CH ch] bf16 in MEMORY order (channels
 // contiguous), CH = 64 or 128, i.e. 128-B or 256-B rows of 16-B chunks.

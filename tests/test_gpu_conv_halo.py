@@ -38,6 +38,14 @@ SHAPES = [
     (2, 128, 128, 16, 32),   # 2x2 tiles: every border kind, batch boundary
     (3, 64, 128, 8, 16),     # one tile per image, 128-B rows, halo all outside
     (2, 128, 64, 24, 48),    # an interior tile with no zero halo; Cout < N tile
+    # Cout 40 is whole 16-B chunks: without a skip the wide epilogue with
+    # three n chunks of the block past Cout
+    (1, 64, 40, 8, 16),
+    (1, 128, 40, 8, 16),
+    # Cout % 8 != 0: the scalar epilogue with and, as no other case, without
+    # a skip (conv_halo_kernel<CIN, 4, false, false>)
+    (1, 64, 44, 8, 16),
+    (1, 128, 44, 8, 16),
 ]
 RAGGED = (1, 128, 128, 12, 20)
 

@@ -14,29 +14,10 @@
 //     (tap +1) pixels for Wo in {32, 64, 128, 256} and every chunk start;
 //  5. the chunk rule gives multiples of 128.
 // Exit status 0 = all checks passed.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
+#include "geo_check.h"
 #include "wgrad_row_geo.h"
 
 using namespace rthd;
-
-static int g_fail = 0;
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      if (g_fail < 20) {                                  \
-        std::printf("FAIL %s:%d: ", __FILE__, __LINE__);  \
-        std::printf(__VA_ARGS__);                         \
-        std::printf("\n");                                \
-      }                                                   \
-      ++g_fail;                                           \
-    }                                                     \
-  } while (0)
-
-static int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // X image of CH channels: fill vs shifted reads, and the conflict ways
 static int check_x_image(int CH) {
@@ -80,31 +61,12 @@ static int check_x_image(int CH) {
                                                         CH) + 32 * CH * 2,
                   "k-block 1 is not k-block 0 + 32 rows");
           }
-          for (int lane = 0; lane < 64; ++lane) {
-            const int g = lane >> 4, i = lane & 15;
-            for (int q = 0; q < 4; ++q) {
-              const int a = addr[16 * g + 4 * q + (i >> 2)] + 2 * (i & 3);
-              const int got = inv[a / 2];
-              const int j = 4 * h + q;
-              const int want =
-                  ((WROW_APRON + dx + 32 * ks + 8 * g + j) << 8) |
-                  (16 * frag + i);
-              CHECK(got == want, "compose CH=%d dx %d frag %d ks %d lane %d "
-                    "j %d: row %d ch %d, want row %d ch %d", CH, dx, frag, ks,
-                    lane, j, got >> 8, got & 255, want >> 8, want & 255);
-            }
-          }
-          for (int half = 0; half < 2; ++half) {
-            std::vector<std::vector<int>> on_bank(64);
-            for (int l = 0; l < 32; ++l)
-              for (int d = 0; d < 2; ++d) {
-                const int a = addr[half * 32 + l] + 4 * d;
-                auto& v = on_bank[(a / 4) % 64];
-                if (std::find(v.begin(), v.end(), a) == v.end())
-                  v.push_back(a);
-              }
-            for (auto& v : on_bank) worst = std::max(worst, (int)v.size());
-          }
+          char what[64];
+          std::snprintf(what, sizeof what, "CH=%d dx %d frag %d ks %d", CH,
+                        dx, frag, ks);
+          tr_check_compose(addr, inv, WROW_APRON + dx + 32 * ks, h, 16 * frag,
+                           what);
+          worst = std::max(worst, tr_read_ways(addr));
         }
   return worst;
 }
@@ -273,10 +235,5 @@ int main() {
     check_shape(s, 64, 128);   // the tile wgrad_row.hip is instantiated at
     check_shape(s, 128, 64);
   }
-  if (g_fail) {
-    std::printf("%d checks FAILED\n", g_fail);
-    return 1;
-  }
-  std::printf("all geometry checks passed\n");
-  return 0;
+  return geo_report();
 }

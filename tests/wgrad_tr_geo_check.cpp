@@ -8,31 +8,14 @@
 //     reads), and the stores cover the tile exactly once;
 //  3. stores and transposed reads compose to k = 8g + j, m = lane & 15;
 //  4. the transposed reads are conflict-free per 32-lane half under the
-//     64-bank rule (bank = (addr / 4) % 64); the ways are printed.
+//     64-bank rule (bank = (addr / 4) % 64); the ways are printed;
+//  5. xcd_cell_remap is a permutation of 0 .. G - 1 for grid sizes G that
+//     are and are not multiples of NUM_XCD, and one just above it.
 // Exit status 0 = all checks passed.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
+#include "geo_check.h"
 #include "wgrad_tr_geo.h"
 
 using namespace rthd;
-
-static int g_fail = 0;
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      if (g_fail < 20) {                                  \
-        std::printf("FAIL %s:%d: ", __FILE__, __LINE__);  \
-        std::printf(__VA_ARGS__);                         \
-        std::printf("\n");                                \
-      }                                                   \
-      ++g_fail;                                           \
-    }                                                     \
-  } while (0)
-
-static int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // LDS image checks of one operand tile of CH channels; fills inv[] with
 // (row << 8 | channel) of every 2-byte element
@@ -70,31 +53,10 @@ static int check_tile_image(int CH, std::vector<int>* inv) {
           CHECK(addr[lane] % 8 == 0 && addr[lane] >= 0 &&
                 addr[lane] + 8 <= bytes, "read addr %d", addr[lane]);
         }
-        // hardware gather: lane i of group g, element q <- column i of the
-        // row whose address lanes 4q .. 4q+3 of the group supply
-        for (int lane = 0; lane < 64; ++lane) {
-          const int g = lane >> 4, i = lane & 15;
-          for (int q = 0; q < 4; ++q) {
-            const int a = addr[16 * g + 4 * q + (i >> 2)] + 2 * (i & 3);
-            const int got = (*inv)[a / 2];
-            const int j = 4 * h + q;
-            const int want = ((32 * ks + 8 * g + j) << 8) | (16 * frag + i);
-            CHECK(got == want, "compose CH=%d frag %d ks %d lane %d j %d: "
-                  "row %d ch %d, want row %d ch %d", CH, frag, ks, lane, j,
-                  got >> 8, got & 255, want >> 8, want & 255);
-          }
-        }
-        // conflict ways per 32-lane half
-        for (int half = 0; half < 2; ++half) {
-          std::vector<std::vector<int>> on_bank(64);
-          for (int l = 0; l < 32; ++l)
-            for (int d = 0; d < 2; ++d) {
-              const int a = addr[half * 32 + l] + 4 * d;
-              auto& v = on_bank[(a / 4) % 64];
-              if (std::find(v.begin(), v.end(), a) == v.end()) v.push_back(a);
-            }
-          for (auto& v : on_bank) worst = std::max(worst, (int)v.size());
-        }
+        char what[64];
+        std::snprintf(what, sizeof what, "CH=%d frag %d ks %d", CH, frag, ks);
+        tr_check_compose(addr, *inv, 32 * ks, h, 16 * frag, what);
+        worst = std::max(worst, tr_read_ways(addr));
       }
   return worst;
 }
@@ -186,7 +148,19 @@ static void check_shape(const Shape& s, int BM, int BN) {
         s.min_steps, max_steps);
 }
 
+static void check_xcd_remap(int G) {
+  std::vector<int> hits(G, 0);
+  for (int cell = 0; cell < G; ++cell) {
+    const int c = xcd_cell_remap(cell, G);
+    CHECK(c >= 0 && c < G, "G=%d: block %d -> cell %d", G, cell, c);
+    if (c >= 0 && c < G) ++hits[c];
+  }
+  for (int c = 0; c < G; ++c)
+    CHECK(hits[c] == 1, "G=%d: cell %d is taken %d times", G, c, hits[c]);
+}
+
 int main() {
+  for (int G : {8, 9, 15, 64, 509, 4608}) check_xcd_remap(G);
   std::vector<int> inv;
   for (int CH : {64, 128}) {
     const int ways = check_tile_image(CH, &inv);
@@ -210,10 +184,5 @@ int main() {
   };
   // the tile the kernel is instantiated at (wgrad_tr.hip: WTR_BM x WTR_BN)
   for (const Shape& s : shapes) check_shape(s, 64, 128);
-  if (g_fail) {
-    std::printf("%d checks FAILED\n", g_fail);
-    return 1;
-  }
-  std::printf("all geometry checks passed\n");
-  return 0;
+  return geo_report();
 }
