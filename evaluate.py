@@ -1,9 +1,10 @@
 """Single-image demo CLI (reference /root/reference/evaluate.py:245-290).
 
 python evaluate.py --data img.jpg --model-load WEIGHTS/check_point_N.pth \
-    --imsize 512 [--conf-th 0.3 --fontsize 10]
+    --imsize 512 [--conf-th 0.3 --fontsize 10] [--device-preprocess]
 
-Loads the image, predicts, draws colored boxes (+class/score text when
+Loads the image (with --device-preprocess the raw frame is uploaded and the
+device resizes and normalises it, same pixels), predicts, draws colored boxes (+class/score text when
 --fontsize > 0), prints the detections and saves ``image.png`` resized back
 to the original size under --save-path.
 """
@@ -11,10 +12,14 @@ to the original size under --save-path.
 import os
 import time
 
+import numpy as np
 import torch
+from PIL import Image
 
+from real_time_helmet_detection_amd import ops
 from real_time_helmet_detection_amd.config import get_arguments
 from real_time_helmet_detection_amd.data import INDEX2CLASS
+from real_time_helmet_detection_amd.data.voc import frames_to_canvas
 from real_time_helmet_detection_amd.utils import (imload, draw_box,
                                                   write_text, ten2pil)
 from real_time_helmet_detection_amd.engine.trainer import load_network
@@ -33,8 +38,21 @@ if __name__ == '__main__':
         pool_size=args.pool_size, flip_test=args.flip_test).to(device)
     predictor.eval()
 
-    img_ten, origin_size = imload(args.data, imsize, args.pretrained)
-    box_ten, cls_ten, score_ten = predictor(img_ten.to(device))
+    if args.device_preprocess:
+        # raw uint8 frame to the device, which resizes and normalises it
+        # bit-identically to imload's Pillow path
+        frame = np.asarray(Image.open(args.data).convert('RGB'))
+        origin_size = (frame.shape[1], frame.shape[0])
+        canvas, sizes = frames_to_canvas([frame], imsize)
+        img_ten = ops.resize_images(canvas.to(device), sizes, imsize,
+                                    args.pretrained)
+        if not img_ten.is_cuda:
+            img_ten = img_ten.contiguous()
+    else:
+        img_ten, origin_size = imload(args.data, imsize, args.pretrained)
+        img_ten = img_ten.to(device)
+    box_ten, cls_ten, score_ten = predictor(img_ten)
+    img_ten = img_ten.cpu()
     box_lst = box_ten[0].tolist()
     cls_lst = cls_ten[0].tolist()
     score_lst = score_ten[0].tolist()

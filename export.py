@@ -5,7 +5,11 @@ python export.py --model-load WEIGHTS/check_point_100.pth [arch flags]
 Uses build_parser (NOT get_arguments): arch flags must be passed manually,
 matching the reference contract. Produces jit_traced_model_cpu.pth and (when
 a GPU is present) jit_traced_model_gpu.pth in --save-path, consumed by the
-in-repo C++ LibTorch app (tools/cpp_infer).
+in-repo C++ LibTorch app (tools/cpp_infer). With ``--raw-input`` (and a
+GPU) it also saves jit_traced_model_gpu_raw.pth, which takes one raw
+(H,W,3) uint8 frame of any size, resizes and normalises it on the device
+(bit-identical to the Python evaluation's Pillow resize) and returns the boxes
+in the frame's own pixels (tools/cpp_infer ``-r``).
 """
 
 import torch
@@ -21,4 +25,6 @@ if __name__ == '__main__':
     network, _, _, _ = load_network(args, device)
     predictor = build_export_module(args, network)
     export_model(predictor, save_dir=args.save_path,
-                 imsize=args.imsize or 512)
+                 imsize=args.imsize or 512,
+                 raw_input=getattr(args, 'raw_input', False),
+                 pretrained=args.pretrained)

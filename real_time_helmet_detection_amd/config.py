@@ -9,11 +9,17 @@ the 11 architecture flags from the checkpoint's sidecar pickle
 
 MI355X-specific additions live in their own group (``--engine``,
 ``--bucket-cap-mb``, ``--comm-dtype``, ``--channels-last``,
-``--device-encode``, ``--device-augment``, ``--synthetic``):
+``--device-encode``, ``--device-augment``, ``--device-preprocess``,
+``--synthetic``):
 they control the HIP kernel engine and the RCCL-over-xGMI gradient bucketing
 and default to the MI355X-native path. ``--flip-test`` (evaluation/demo
 group, default off) is an evaluation option, not an architecture flag: it is
-never restored from a checkpoint's sidecar.
+never restored from a checkpoint's sidecar. Neither is
+``--device-preprocess`` (default off, evaluation and demo only, ignored with
+a notice under ``--train-flag``): raw uint8 frames go to the device, which
+resizes and normalises them bit-identically to the workers' Pillow path.
+``export.py`` alone reads ``--raw-input`` (default off): it additionally
+saves a GPU trace that takes the raw frame.
 """
 
 import os
@@ -203,6 +209,19 @@ def make_parser():
                  'device, which also writes the normalised image '
                  '(single-pass bilinear: pixels differ slightly from the '
                  'three-pass worker chain)')
+    parser.add_argument('--device-preprocess', dest='device_preprocess',
+            action='store_true', default=False,
+            help='evaluation and demo only: the workers ship the raw uint8 '
+                 'frames and the device resizes them to --imsize and '
+                 'normalises them in one pass, bit-identical to the '
+                 "workers' Pillow resize (the antialiased bilinear filter); "
+                 'ignored with --train-flag')
+    parser.add_argument('--raw-input', dest='raw_input',
+            action='store_true', default=False,
+            help='export.py only: also save jit_traced_model_gpu_raw.pth, '
+                 'a GPU trace that takes one raw (H,W,3) uint8 frame of any '
+                 'size, preprocesses it on the device and returns boxes in '
+                 "the frame's pixels (needs the kernel extension)")
     parser.add_argument('--synthetic', action='store_true', default=False,
             help='use synthetic VOC2028-shaped data (no dataset on disk)')
     parser.add_argument('--synthetic-size', type=int, default=512,
@@ -215,6 +234,10 @@ def build_parser(argv=None):
     args = make_parser().parse_args(argv)
     if args.device_augment:
         args.device_encode = True
+    if args.device_preprocess and args.train_flag:
+        print('--device-preprocess is an evaluation/demo option: ignored '
+              'with --train-flag')
+        args.device_preprocess = False
     return args
 
 

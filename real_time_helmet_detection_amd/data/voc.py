@@ -17,6 +17,9 @@ Capability parity with /root/reference/data.py:22-125:
 - ``collate_device_aug`` -> (img_u8 canvas, sizes, coef, T, boxes, labels,
   voc_dict_list): the opt-in ``--device-augment`` form, which leaves the
   pixel half of the train augmentation to the device as well.
+- ``collate_frames`` -> (img_u8 canvas, sizes, voc_dict_list): the opt-in
+  ``--device-preprocess`` form for evaluation, which leaves the resize and
+  the normalisation to the device (ops.resize_images).
 
 ``SyntheticVOC`` generates VOC2028-shaped data in memory (random images,
 random plausible hat/person boxes, same voc_dict contract) for the
@@ -32,6 +35,7 @@ import torch
 
 from ..transform import box2hm
 from ..utils import get_normalizer
+from ..ops.functional import RESIZE_MAX_RATIO
 
 CLASS2INDEX = {'hat': 0, 'person': 1, 'dog': 0}
 INDEX2CLASS = {0: 'hat', 1: 'person'}
@@ -104,6 +108,35 @@ def pack_boxes(boxes_lst, labels_lst, multiple=8):
     return torch.from_numpy(boxes_t), torch.from_numpy(labels_t)
 
 
+# per-axis size ratio to the target above which frames_to_canvas resizes in
+# the worker (the device kernel's cap)
+DEVICE_RESIZE_MAX_RATIO = RESIZE_MAX_RATIO
+
+
+def frames_to_canvas(imgs, T):
+    """Raw (h,w,3) uint8 arrays -> (canvas (B,Hmax,Wmax,3) uint8 with image
+    b in its top-left corner, sizes (B,2) int32 [h, w]): the input of
+    ops.resize_images. An image more than DEVICE_RESIZE_MAX_RATIO times T
+    on either axis is resized here with Pillow to T x T and placed as a
+    T x T image; the device pass on it is then the identity, so the result
+    is the worker path's for every input."""
+    from PIL import Image
+    imgs = list(imgs)
+    limit = DEVICE_RESIZE_MAX_RATIO * T
+    for i, im in enumerate(imgs):
+        if max(im.shape[:2]) > limit:
+            imgs[i] = np.asarray(
+                Image.fromarray(np.ascontiguousarray(im)).resize(
+                    (T, T), Image.BILINEAR))
+    hmax = max(im.shape[0] for im in imgs)
+    wmax = max(im.shape[1] for im in imgs)
+    canvas = np.zeros((len(imgs), hmax, wmax, 3), dtype=np.uint8)
+    for i, im in enumerate(imgs):
+        canvas[i, :im.shape[0], :im.shape[1]] = im
+    sizes = np.asarray([im.shape[:2] for im in imgs], dtype=np.int32)
+    return torch.from_numpy(canvas), torch.from_numpy(sizes.reshape(-1, 2))
+
+
 class _CollateMixin:
     """Shared collate: batch augmentation -> heatmap encode -> tensors."""
 
@@ -170,6 +203,16 @@ class _CollateMixin:
         return (torch.from_numpy(canvas), torch.from_numpy(sizes),
                 torch.from_numpy(coef), target, boxes_t, labels_t,
                 list(voc_dicts))
+
+    def collate_frames(self, batch):
+        """--device-preprocess (evaluation): no transform call, no
+        normalise, no target encoding. Returns (canvas (B,Hmax,Wmax,3)
+        uint8, sizes (B,2) int32 [h, w], voc_dict_list) for
+        ops.resize_images to resize to the TestAugmentor's imsize and
+        normalise on the device (see frames_to_canvas)."""
+        imgs, _, _, voc_dicts = zip(*batch)
+        canvas, sizes = frames_to_canvas(imgs, int(self.transform.imsize))
+        return canvas, sizes, list(voc_dicts)
 
     def collate_fn(self, batch):
         imgs, boxes_lst, labels_lst, voc_dicts = zip(*batch)

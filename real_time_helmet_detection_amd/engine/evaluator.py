@@ -158,12 +158,25 @@ def evaluate_step(dataloader, predictor, device, args):
     imsize = args.imsize or args.multiscale[1]
 
     tictoc = time.time()
-    for image, gt_heatmap, gt_offset, gt_size, gt_mask, gt_dict in \
-            tqdm(dataloader):
+    device_preprocess = getattr(args, 'device_preprocess', False)
+    for batch in tqdm(dataloader):
         time_logger['data'].update(time.time() - tictoc)
 
         tictoc = time.time()
-        box_lst, cls_lst, score_lst = predictor(image.to(device))
+        gt_dict = batch[-1]
+        if device_preprocess:
+            # a collate_frames batch: raw uint8 canvas + sizes; the device
+            # (the eager oracle on CPU) resizes and normalises
+            canvas, sizes = batch[0], batch[1]
+            image = ops.resize_images(canvas.to(device), sizes, imsize,
+                                      args.pretrained)
+            if not image.is_cuda:
+                # the CPU network is fed NCHW-contiguous batches without
+                # the flag; its convolutions round differently on NHWC
+                image = image.contiguous()
+        else:
+            image = batch[0].to(device)
+        box_lst, cls_lst, score_lst = predictor(image)
         time_logger['forward'].update(time.time() - tictoc)
 
         for b in range(image.shape[0]):
@@ -220,7 +233,9 @@ def single_device_evaluate(args):
     dataset = load_dataset(args)
     dataloader = torch.utils.data.DataLoader(
         dataset=dataset, batch_size=args.batch_size, shuffle=False,
-        num_workers=args.num_workers, collate_fn=dataset.collate_fn)
+        num_workers=args.num_workers,
+        collate_fn=dataset.collate_frames
+        if getattr(args, 'device_preprocess', False) else dataset.collate_fn)
 
     predictions = evaluate_step(dataloader, predictor, device, args)
 

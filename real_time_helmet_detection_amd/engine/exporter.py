@@ -203,6 +203,31 @@ class Export(torch.nn.Module):
         return boxes[keep], clss[keep], scores[keep]
 
 
+class RawExport(torch.nn.Module):
+    """Raw-frame front end of ``Export`` for the GPU-native trace: one
+    (H,W,3) uint8 device frame of any size -> rthd::resize_frame (the
+    Pillow-exact resize to ``imsize`` and the normalise, one pass on the
+    device) -> ``Export`` -> (boxes in the frame's own pixels, classes,
+    scores). The op reads H and W from the tensor when it runs, so a trace
+    holds nothing about the example frame's size."""
+
+    def __init__(self, export, imsize, pretrained='imagenet'):
+        super().__init__()
+        from ..ops import hip
+        self.export = export
+        self.imsize = int(imsize)
+        self.register_buffer(
+            'table', hip._norm_table(torch.device('cuda',
+                                                  torch.cuda.current_device()),
+                                     pretrained, torch.float32).clone())
+
+    def forward(self, frame):
+        image, scale = torch.ops.rthd.resize_frame(frame, self.imsize,
+                                                   self.table)
+        boxes, clss, scores = self.export(image)
+        return boxes * scale, clss, scores
+
+
 def build_export_module(args, network):
     return Export(
         network=network, topk=args.topk, scale_factor=args.scale_factor,
@@ -213,7 +238,7 @@ def build_export_module(args, network):
 
 
 def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,
-                 native=True):
+                 native=True, raw_input=False, pretrained='imagenet'):
     """Trace and save cpu (and, if available, gpu) TorchScript models.
 
     The CPU trace records plain torch-ROCm eager ops — self-contained and
@@ -224,6 +249,11 @@ def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,
     into the graph as constants; the consumer (tools/cpp_infer, ``-k``)
     dlopens the kernel extension before loading. Pass ``native=False`` (or
     set RTHD_EXPORT_EAGER=1) for a portable eager-op GPU trace instead.
+
+    ``raw_input`` additionally saves jit_traced_model_gpu_raw.pth, the
+    native GPU trace behind ``RawExport``: it takes the raw uint8 frame and
+    normalises with the ``pretrained`` scheme. The other files are the same
+    with and without it.
     """
     import os
     os.makedirs(save_dir, exist_ok=True)
@@ -262,6 +292,20 @@ def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,
             paths['gpu'] = p
             print('Model saved at gpu (%s ops): %s'
                   % ('native rthd' if native else 'eager', p))
+            if raw_input:
+                if not native:
+                    raise RuntimeError('the raw-input export records the '
+                                       'native rthd ops: no eager variant')
+                raw = RawExport(predictor, imsize, pretrained).cuda().eval()
+                frame = torch.randint(0, 256, (imsize, imsize, 3),
+                                      dtype=torch.uint8, device='cuda')
+                with torch.no_grad():
+                    traced_raw = torch.jit.trace(raw, frame)
+                p = os.path.join(save_dir, 'jit_traced_model_gpu_raw.pth')
+                torch.jit.save(traced_raw, p)
+                paths['gpu_raw'] = p
+                print('Raw-input model saved at gpu: %s (takes a (H,W,3) '
+                      'uint8 frame; needs the kernel extension to load)' % p)
         finally:
             if prev is None:
                 os.environ.pop('RTHD_EAGER_GPU', None)

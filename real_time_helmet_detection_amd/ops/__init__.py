@@ -90,5 +90,11 @@ def soft_nms_batched(boxes, scores, sigma, score_th, conf_th):
     return eager.soft_nms_batched(boxes, scores, sigma, score_th, conf_th)
 
 
+def resize_images(img_u8, sizes, T, pretrained=None, dtype=torch.float32):
+    # --device-preprocess: Pillow-exact resize (+ normalise) of raw frames
+    from . import functional
+    return functional.resize_images(img_u8, sizes, T, pretrained, dtype)
+
+
 def available():
     return _backend.ext() is not None

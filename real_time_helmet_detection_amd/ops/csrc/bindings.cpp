@@ -152,6 +152,12 @@ int64_t encode_chunk();
 torch::Tensor augment_u8(torch::Tensor img_u8, torch::Tensor sizes,
                          torch::Tensor coef, int64_t T,
                          c10::optional<torch::Tensor> table);
+torch::Tensor resize_u8(torch::Tensor img_u8, torch::Tensor sizes, int64_t T,
+                        c10::optional<torch::Tensor> table);
+std::tuple<torch::Tensor, torch::Tensor> resize_frame(torch::Tensor frame_u8,
+                                                      int64_t T,
+                                                      torch::Tensor table);
+int64_t resize_max_ratio();
 }  // namespace rthd
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -211,6 +217,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("encode_chunk", &rthd::encode_chunk);
   m.def("augment_u8", &rthd::augment_u8, py::arg("img_u8"), py::arg("sizes"),
         py::arg("coef"), py::arg("T"), py::arg("table") = py::none());
+  m.def("resize_u8", &rthd::resize_u8, py::arg("img_u8"), py::arg("sizes"),
+        py::arg("T"), py::arg("table") = py::none());
+  m.def("resize_frame", &rthd::resize_frame);
+  m.def("resize_max_ratio", &rthd::resize_max_ratio);
 }
 
 // ---------------------------------------------------------------------------
@@ -295,6 +305,10 @@ TORCH_LIBRARY(rthd, m) {
         "int pool_size, bool normalized, bool flip) "
         "-> (Tensor, Tensor, Tensor)");
   m.def("stem_im2col(Tensor x, int ks, int stride, int pad) -> Tensor");
+  m.def("resize_u8(Tensor img_u8, Tensor sizes, int T, Tensor? table) "
+        "-> Tensor");
+  m.def("resize_frame(Tensor frame_u8, int T, Tensor table) "
+        "-> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(rthd, CUDA, m) {
@@ -312,4 +326,6 @@ TORCH_LIBRARY_IMPL(rthd, CUDA, m) {
   m.impl("decode", rthd::decode_op);
   m.impl("decode_logits", rthd::decode_logits_op);
   m.impl("stem_im2col", rthd::stem_im2col);
+  m.impl("resize_u8", rthd::resize_u8);
+  m.impl("resize_frame", rthd::resize_frame);
 }

@@ -7,6 +7,8 @@ to these silently — dispatch in ``ops/__init__`` raises if the HIP extension
 is missing for a CUDA tensor.
 """
 
+import functools
+
 import torch
 import torch.nn.functional as F
 
@@ -136,6 +138,105 @@ def augment_images(img_u8, sizes, coef, T, pretrained=None,
     if pretrained is None:
         return q
     return normalize_images(q, pretrained, dtype)
+
+
+_RESIZE_PREC = 22  # coefficient precision bits of the 8-bit resample
+
+
+@functools.lru_cache(maxsize=64)
+def _resize_coefficients(n, T):
+    """Pillow's 8-bit bilinear coefficients for one axis, n -> T, in float64
+    with every operation rounded on its own: (xmin (T,), xmax (T,),
+    k (T, K) int64 with zeros past xmax)."""
+    f64 = torch.float64
+    scale = torch.tensor(float(n), dtype=f64) / torch.tensor(float(T),
+                                                             dtype=f64)
+    fs = torch.clamp(scale, min=1.0)
+    support = fs
+    K = int(torch.ceil(support).item()) * 2 + 1
+    center = (torch.arange(T, dtype=f64) + 0.5) * scale
+    xmin = (center - support + 0.5).to(torch.int64).clamp(min=0)
+    xmax = (center + support + 0.5).to(torch.int64).clamp(max=n) - xmin
+    x = torch.arange(K, dtype=torch.int64)[None, :]
+    t = ((x + xmin[:, None]).to(f64) - center[:, None] + 0.5) / fs
+    w = torch.clamp(1.0 - t.abs(), min=0.0)
+    w = torch.where(x < xmax[:, None], w, torch.zeros_like(w))
+    ww = torch.zeros(T, dtype=f64)
+    for j in range(K):  # summed in tap order; a masked tap adds an exact 0
+        ww = ww + w[:, j]
+    ww = torch.where(ww != 0.0, ww, torch.ones_like(ww))[:, None]
+    k = (0.5 + (w / ww) * float(1 << _RESIZE_PREC)).to(torch.int64)
+    k = torch.where(x < xmax[:, None], k, torch.zeros_like(k))
+    return xmin, xmax, k
+
+
+def _resize_pass(img, dim, T):
+    """One axis of the 8-bit resample: img (h,w,3) uint8 -> size T along
+    ``dim`` (0 = vertical, 1 = horizontal), int64 accumulation."""
+    n = img.shape[dim]
+    xmin, xmax, k = (t.to(img.device) for t in _resize_coefficients(n, T))
+    shape = [1, 1, 1]
+    shape[dim] = T
+    acc = torch.full(shape, 1 << (_RESIZE_PREC - 1), dtype=torch.int64,
+                     device=img.device)
+    for j in range(int(xmax.max())):
+        idx = (xmin + j).clamp(max=n - 1)  # clamped taps have k == 0
+        acc = acc + img.index_select(dim, idx).to(torch.int64) \
+            * k[:, j].view(shape)
+    return (acc >> _RESIZE_PREC).clamp(0, 255).to(torch.uint8)
+
+
+def check_resize_args(img_u8, sizes, T):
+    """Host-side argument checks of resize_images on a CPU copy of
+    ``sizes`` (no device sync): every image fits its canvas."""
+    hmax, wmax = int(img_u8.shape[1]), int(img_u8.shape[2])
+    if int(T) < 1:
+        raise ValueError('resize_images: T must be >= 1, got %r' % (T,))
+    if sizes.dim() != 2 or tuple(sizes.shape) != (img_u8.shape[0], 2):
+        raise ValueError('resize_images: sizes must be (B,2), got %r'
+                         % (tuple(sizes.shape),))
+    if sizes.numel():
+        h, w = sizes[:, 0], sizes[:, 1]
+        if int(h.min()) < 1 or int(h.max()) > hmax or int(w.min()) < 1 \
+                or int(w.max()) > wmax:
+            raise ValueError('resize_images: sizes must satisfy 1 <= h <= '
+                             '%d and 1 <= w <= %d' % (hmax, wmax))
+
+
+def resize_images(img_u8, sizes, T, pretrained=None, dtype=torch.float32):
+    """Serving preprocess (the oracle of ops/csrc/preprocess.hip): every
+    image of the batch resized to (T, T) exactly as
+    PIL.Image.resize((T, T), BILINEAR) does it on 8-bit data.
+
+    img_u8 (B,Hmax,Wmax,3) uint8 with image b in its top-left sizes[b] =
+    [h, w] corner (the rest of the canvas is never read). Per axis (input
+    size n), in float64:
+
+        scale = n / T;  fs = max(scale, 1);  support = fs
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n) - xmin
+        w[x] = max(1 - |x + xmin - center + 0.5| / fs, 0), normalised by
+               their sum in tap order;  k[x] = int(0.5 + w[x] * 2^22)
+        out = clamp((2^21 + sum_x pixel[xmin + x] * k[x]) >> 22, 0, 255)
+
+    horizontal pass first, rounded to uint8, then the vertical pass over it.
+
+    pretrained=None returns (B,T,T,3) uint8; otherwise
+    normalize_images(q, pretrained, dtype)."""
+    T = int(T)
+    if not sizes.is_cuda:
+        check_resize_args(img_u8, sizes, T)
+    hmax, wmax = img_u8.shape[1:3]
+    out = torch.empty((img_u8.shape[0], T, T, 3), dtype=torch.uint8,
+                      device=img_u8.device)
+    for b, (h, w) in enumerate(sizes.tolist()):
+        h = min(max(int(h), 1), hmax)
+        w = min(max(int(w), 1), wmax)
+        out[b] = _resize_pass(_resize_pass(img_u8[b, :h, :w], 1, T), 0, T)
+    if pretrained is None:
+        return out
+    return normalize_images(out, pretrained, dtype)
 
 
 # ---------------------------------------------------------------- conv-ish --

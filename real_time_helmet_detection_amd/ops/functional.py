@@ -157,6 +157,28 @@ def augment_images(img_u8, sizes, coef, T, pretrained=None,
     return eager.augment_images(img_u8, sizes, coef, T, pretrained, dtype)
 
 
+# largest per-axis minification ceil(n / T) resize_images takes on the device
+# (RS_MAX_RATIO of ops/csrc/preprocess.hip, which refuses anything larger)
+RESIZE_MAX_RATIO = 16
+
+
+def resize_images(img_u8, sizes, T, pretrained=None, dtype=torch.float32):
+    """--device-preprocess: the evaluation resize of data.augment.
+    TestAugmentor, PIL's antialiased 8-bit Image.resize((T, T), BILINEAR),
+    for a batch of raw frames of different sizes, bit for bit.
+
+    img_u8 (B,Hmax,Wmax,3) uint8 canvas with image b in its top-left
+    sizes[b] corner, sizes (B,2) int32 [h, w], T the square output side.
+    Returns (B,T,T,3) uint8 when ``pretrained`` is None, else the normalised
+    (B,3,T,T) channels_last tensor of ``dtype``: the evaluation collate's
+    image (fp32), or that cast to bf16."""
+    if _hip(img_u8):
+        from . import hip
+        return hip.resize_images(img_u8, sizes, T, pretrained, dtype)
+    from . import eager
+    return eager.resize_images(img_u8, sizes, T, pretrained, dtype)
+
+
 def upsample2x_add(x, skip=None):
     """Nearest 2x upsample, optionally fused with the hourglass skip add."""
     if _hip(x):

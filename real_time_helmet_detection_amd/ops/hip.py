@@ -755,6 +755,27 @@ def augment_images(img_u8, sizes, coef, T, pretrained=None,
     return _C().augment_u8(img_u8, sizes, coef, int(T), table)
 
 
+def resize_images(img_u8, sizes, T, pretrained=None, dtype=torch.float32):
+    """Device twin of ops.eager.resize_images (ops/csrc/preprocess.hip): the
+    Pillow-exact 8-bit bilinear resize of a raw uint8 canvas batch to
+    (T, T), as uint8 (pretrained=None) or as the normalised channels_last
+    fp32 / bf16 image. ``sizes`` still on the host is checked there and
+    uploaded without blocking; a device copy is trusted and never read back
+    (the kernels clamp every address into the canvas regardless), so the
+    call is legal under stream capture."""
+    from .eager import check_resize_args
+    if pretrained is not None and dtype not in (torch.float32,
+                                                torch.bfloat16):
+        raise ValueError('resize_images: dtype must be float32 or '
+                         'bfloat16, got %r' % (dtype,))
+    if not sizes.is_cuda:
+        check_resize_args(img_u8, sizes, T)
+    sizes = sizes.to(img_u8.device, non_blocking=True)
+    table = None if pretrained is None else \
+        _norm_table(img_u8.device, pretrained, dtype)
+    return _C().resize_u8(img_u8, sizes, int(T), table)
+
+
 # ---------------------------------------------------------------- decode ---
 
 def batched_decode(heatmap, offset, wh, scale_factor, topk, pool_size,

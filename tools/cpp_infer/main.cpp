@@ -10,8 +10,20 @@
 // The app depends only on LibTorch: images are binary PPM (P6), the
 // zero-dependency format every tool can emit (`convert img.jpg img.ppm`,
 // or `python tools/cpp_infer/to_ppm.py img.jpg`). Preprocessing matches
-// utils.imload: resize to 512x512 (bilinear), scale to [0,1], ImageNet
-// normalize.
+// utils.imload in layout only: resize to 512x512, scale to [0,1], ImageNet
+// normalize. The resize here is at::upsample_bilinear2d, a plain 2-tap
+// filter WITHOUT antialiasing, while the Python path (Pillow BILINEAR) widens
+// its filter with the ratio on a downscale: for a frame larger than the
+// network input this app feeds the network different pixels than the Python
+// evaluation did.
+//
+//   ./helmet_infer -r -m jit_traced_model_gpu_raw.pth -k <_C*.so> -i image.ppm
+//
+// -r closes that gap: the PPM goes to the model as the uint8 HWC tensor it
+// was read into, the raw-input trace (export.py --raw-input) resizes and
+// normalises it on the device bit-identically to the Python path, and the
+// boxes are printed in the source image's pixels. GPU only; -s is unused
+// (the size is baked into the trace).
 // When the traced GPU model embeds the native gfx950 ops (torch.ops.rthd.*,
 // the default export.py GPU trace), pass the kernel extension with
 // -k <path to real_time_helmet_detection_amd/ops/_C*.so>; it is dlopen'd
@@ -72,7 +84,10 @@ static torch::Tensor load_image(const std::string& path, int imsize) {
 static int run(int argc, char** argv) {
   std::string model_path, image_path, kernels_path;
   int iters = 100, imsize = 512;
-  for (int i = 1; i < argc - 1; ++i) {
+  bool raw = false;
+  for (int i = 1; i < argc; ++i) {
+    if (!strcmp(argv[i], "-r")) { raw = true; continue; }
+    if (i >= argc - 1) break;  // every other flag takes a value
     if (!strcmp(argv[i], "-m")) model_path = argv[++i];
     else if (!strcmp(argv[i], "-i")) image_path = argv[++i];
     else if (!strcmp(argv[i], "-k")) kernels_path = argv[++i];
@@ -82,7 +97,7 @@ static int run(int argc, char** argv) {
   if (model_path.empty() || image_path.empty()) {
     std::cerr << "usage: " << argv[0]
               << " -m model.pth -i image.ppm [-k rthd_ops.so] [-n iters]"
-                 " [-s imsize]\n";
+                 " [-s imsize] [-r]\n";
     return 1;
   }
   if (!kernels_path.empty()) {
@@ -101,7 +116,11 @@ static int run(int argc, char** argv) {
   torch::Device device(cuda ? torch::kCUDA : torch::kCPU);
   model.to(device);
 
-  auto img = load_image(image_path, imsize).to(device);
+  if (raw && !cuda)
+    throw std::runtime_error("-r needs a GPU and a jit_traced_model_gpu_raw "
+                             "model");
+  auto img = raw ? read_ppm(image_path).to(device)
+                 : load_image(image_path, imsize).to(device);
 
   torch::NoGradGuard ng;
   auto out = model.forward({img}).toTuple();
@@ -127,8 +146,13 @@ static int run(int argc, char** argv) {
   if (cuda) at::hip::device_synchronize();
   auto t1 = std::chrono::steady_clock::now();
   const double sec = std::chrono::duration<double>(t1 - t0).count();
-  printf("%d iters in %.3f s -> %.1f FPS @ %dx%d (%s)\n", iters, sec,
-         iters / sec, imsize, imsize, cuda ? "gpu" : "cpu");
+  if (raw)
+    printf("%d iters in %.3f s -> %.1f FPS, raw %lldx%lld frame, "
+           "preprocess included (gpu)\n", iters, sec, iters / sec,
+           (long long)img.size(1), (long long)img.size(0));
+  else
+    printf("%d iters in %.3f s -> %.1f FPS @ %dx%d (%s)\n", iters, sec,
+           iters / sec, imsize, imsize, cuda ? "gpu" : "cpu");
   return 0;
 }
 
