@@ -1,12 +1,14 @@
 """Single-image demo CLI (reference /root/reference/evaluate.py:245-290).
 
 python evaluate.py --data img.jpg --model-load WEIGHTS/check_point_N.pth \
-    --imsize 512 [--conf-th 0.3 --fontsize 10] [--device-preprocess]
+    --imsize 512 [--conf-th 0.3 --fontsize 10] [--device-preprocess] \
+    [--infer-dtype {fp32,bf16,fp8}]
 
 Loads the image (with --device-preprocess the raw frame is uploaded and the
 device resizes and normalises it, same pixels), predicts, draws colored boxes (+class/score text when
 --fontsize > 0), prints the detections and saves ``image.png`` resized back
-to the original size under --save-path.
+to the original size under --save-path. --infer-dtype bf16 / fp8 runs the
+predictor on the bf16 / e4m3 kernels (GPU only; fp32 is the default).
 """
 
 import os
@@ -16,7 +18,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from real_time_helmet_detection_amd import ops
+from real_time_helmet_detection_amd import amp, ops
 from real_time_helmet_detection_amd.config import get_arguments
 from real_time_helmet_detection_amd.data import INDEX2CLASS
 from real_time_helmet_detection_amd.data.voc import frames_to_canvas
@@ -51,7 +53,11 @@ if __name__ == '__main__':
     else:
         img_ten, origin_size = imload(args.data, imsize, args.pretrained)
         img_ten = img_ten.to(device)
-    box_ten, cls_ten, score_ten = predictor(img_ten)
+    if args.infer_dtype == 'fp32':
+        box_ten, cls_ten, score_ten = predictor(img_ten)
+    else:
+        with amp.infer_context(args.infer_dtype):
+            box_ten, cls_ten, score_ten = predictor(img_ten)
     img_ten = img_ten.cpu()
     box_lst = box_ten[0].tolist()
     cls_lst = cls_ten[0].tolist()

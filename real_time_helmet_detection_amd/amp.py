@@ -106,3 +106,18 @@ def fp8_autocast(enabled=True):
         yield
     finally:
         _fp8_depth -= 1
+
+
+def infer_context(infer_dtype='fp32'):
+    """The contexts behind ``--infer-dtype``: nothing for ``fp32``,
+    ``autocast`` for ``bf16``, ``autocast`` plus ``fp8_autocast`` for
+    ``fp8``. Returns a fresh context manager."""
+    if infer_dtype not in ('fp32', 'bf16', 'fp8'):
+        raise ValueError('infer_dtype must be fp32, bf16 or fp8, got %r'
+                         % (infer_dtype,))
+    stack = contextlib.ExitStack()
+    if infer_dtype != 'fp32':
+        stack.enter_context(autocast(True))
+    if infer_dtype == 'fp8':
+        stack.enter_context(fp8_autocast(True))
+    return stack

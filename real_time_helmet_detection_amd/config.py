@@ -19,7 +19,11 @@ never restored from a checkpoint's sidecar. Neither is
 a notice under ``--train-flag``): raw uint8 frames go to the device, which
 resizes and normalises them bit-identically to the workers' Pillow path.
 ``export.py`` alone reads ``--raw-input`` (default off): it additionally
-saves a GPU trace that takes the raw frame.
+saves a GPU trace that takes the raw frame, and ``--serve`` (default off):
+the capture-legal serving trace (raw frame in, packed detections out).
+``--infer-dtype`` (default ``fp32``) picks the precision of evaluation, the
+demo and the GPU exports; it is a per-run choice, kept out of
+``argument.pickle`` both ways, and refused on a CPU run unless ``fp32``.
 """
 
 import os
@@ -38,6 +42,10 @@ ARCH_FLAGS = [
     'num_stack', 'hourglass_inch', 'increase_ch', 'activation', 'pool',
     'neck_activation', 'neck_pool',
 ]
+
+INFER_DTYPES = ('fp32', 'bf16', 'fp8')
+# per-run flags that the sidecar pickle never carries
+TRANSIENT_FLAGS = ('infer_dtype',)
 
 
 def make_parser():
@@ -222,6 +230,18 @@ def make_parser():
                  'a GPU trace that takes one raw (H,W,3) uint8 frame of any '
                  'size, preprocesses it on the device and returns boxes in '
                  "the frame's pixels (needs the kernel extension)")
+    parser.add_argument('--serve', action='store_true', default=False,
+            help='export.py only: also save jit_traced_model_gpu_serve.pth '
+                 '(with the --infer-dtype suffix), the serving trace: one raw '
+                 '(H,W,3) uint8 frame in, one packed (1+N, 6) detection '
+                 'tensor out, no host sync inside, so the consumer may '
+                 'capture it into a graph (needs a GPU and the kernel '
+                 'extension)')
+    parser.add_argument('--infer-dtype', dest='infer_dtype', default='fp32',
+            choices=INFER_DTYPES,
+            help='inference precision of evaluation, the demo and the GPU '
+                 'exports: fp32 (default), bf16 (the bf16 MFMA kernels) or '
+                 'fp8 (bf16 plus the e4m3 serving convs); GPU only')
     parser.add_argument('--synthetic', action='store_true', default=False,
             help='use synthetic VOC2028-shaped data (no dataset on disk)')
     parser.add_argument('--synthetic-size', type=int, default=512,
@@ -231,7 +251,11 @@ def make_parser():
 
 def build_parser(argv=None):
     """Parse argv (public interface parity: reference config.py:11-136)."""
-    args = make_parser().parse_args(argv)
+    parser = make_parser()
+    args = parser.parse_args(argv)
+    if args.infer_dtype != 'fp32' and -1 in args.gpu_no:
+        parser.error('--infer-dtype %s needs a GPU: a CPU run (--gpu-no -1) '
+                     'takes --infer-dtype fp32 only' % args.infer_dtype)
     if args.device_augment:
         args.device_encode = True
     if args.device_preprocess and args.train_flag:
@@ -281,7 +305,9 @@ def get_arguments(argv=None):
     with open(os.path.join(args.save_path, 'argument.txt'), 'w') as f:
         for key, value in sorted(vars(args).items()):
             f.write('%s: %s' % (key, value) + '\n')
-    save_pickle(os.path.join(args.save_path, 'argument.pickle'), vars(args))
+    save_pickle(os.path.join(args.save_path, 'argument.pickle'),
+                {k: v for k, v in vars(args).items()
+                 if k not in TRANSIENT_FLAGS})
     return args
 
 

@@ -21,6 +21,7 @@ from collections import defaultdict
 import numpy as np
 import torch
 
+from .. import amp as rthd_amp
 from .. import ops
 from ..utils import AverageMeter, save_pickle
 from ..data import load_dataset
@@ -159,6 +160,10 @@ def evaluate_step(dataloader, predictor, device, args):
 
     tictoc = time.time()
     device_preprocess = getattr(args, 'device_preprocess', False)
+    # --infer-dtype: bf16 / fp8 run the predictor under the amp contexts
+    infer_dtype = getattr(args, 'infer_dtype', 'fp32')
+    if infer_dtype != 'fp32' and device.type != 'cuda':
+        raise ValueError('--infer-dtype %s needs a GPU' % infer_dtype)
     for batch in tqdm(dataloader):
         time_logger['data'].update(time.time() - tictoc)
 
@@ -176,7 +181,11 @@ def evaluate_step(dataloader, predictor, device, args):
                 image = image.contiguous()
         else:
             image = batch[0].to(device)
-        box_lst, cls_lst, score_lst = predictor(image)
+        if infer_dtype == 'fp32':
+            box_lst, cls_lst, score_lst = predictor(image)
+        else:
+            with rthd_amp.infer_context(infer_dtype):
+                box_lst, cls_lst, score_lst = predictor(image)
         time_logger['forward'].update(time.time() - tictoc)
 
         for b in range(image.shape[0]):

@@ -6,6 +6,10 @@ symbolically, not trace-unrolled) so the traced module is self-contained —
 the C++ inference app (tools/cpp_infer) loads it with LibTorch and needs no
 python. ``export_model`` traces and saves the cpu/gpu variants
 (jit_traced_model_cpu.pth / jit_traced_model_gpu.pth, export.py:120-130).
+``RawExport`` puts the device preprocess in front of it; ``ServeExport`` is
+the serving form: raw frame in, one packed fixed-shape detection tensor out
+(rthd::nms_pack), nothing inside that needs the host, so the consumer can
+replay it from a captured graph.
 """
 
 from typing import Tuple
@@ -149,16 +153,38 @@ class Export(torch.nn.Module):
         ops per stack plus a scripted NMS loop whose float(s[i]) costs one
         device sync per candidate (the eager export ran at 65 FPS in the
         C++ app; this path at 150+)."""
+        return self._nms_native(*self._decode_plain(outputs))
+
+    def _decode_plain(self, outputs):
+        """(S, num_cls+4, h, w) network output of the one image -> the
+        decode kernel's (boxes (S,topk,4), classes, scores)."""
         outs = outputs.float()  # (S, num_cls+4, h, w)
         heatmap, offset, wh = outs.split([self.num_cls, 2, 2], dim=1)
         heatmap = torch.sigmoid(heatmap)
         if self.normalized_coord:
             offset = torch.sigmoid(offset)
             wh = torch.sigmoid(wh)
-        b, c, s = torch.ops.rthd.decode(
+        return torch.ops.rthd.decode(
             heatmap, offset, wh, self.scale_factor, self.topk,
             self.pool_size, self.normalized_coord)
-        return self._nms_native(b, c, s)
+
+    def _decode_flip(self, out):
+        """(2, S, num_cls+4, h, w) output of image and mirror -> the merged
+        logits-in decode."""
+        if out.dtype != torch.bfloat16:
+            out = out.float()
+        return torch.ops.rthd.decode_logits(
+            out.contiguous(), self.scale_factor, self.topk,
+            self.pool_size, self.normalized_coord, True)
+
+    def decode_native(self, x):
+        """Network and native GPU decode of this configuration (plain or
+        flip test), without the NMS: what ``forward`` feeds ``_nms_native``
+        and ``ServeExport`` feeds the packed NMS."""
+        if self.flip_test:
+            return self._decode_flip(
+                self.network(torch.cat([x[:1], x[:1].flip(3)])))
+        return self._decode_plain(self.network(x)[0])
 
     def _nms_native(self, b, c, s):
         boxes = b.reshape(-1, 4)
@@ -181,12 +207,7 @@ class Export(torch.nn.Module):
         from ..ops import eager
         out = self.network(torch.cat([x[:1], x[:1].flip(3)]))
         if out.is_cuda and not _backend.eager_gpu_override():
-            if out.dtype != torch.bfloat16:
-                out = out.float()
-            b, c, s = torch.ops.rthd.decode_logits(
-                out.contiguous(), self.scale_factor, self.topk,
-                self.pool_size, self.normalized_coord, True)
-            return self._nms_native(b, c, s)
+            return self._nms_native(*self._decode_flip(out))
         b, c, s = eager.decode_logits(
             out, self.scale_factor, self.topk, self.pool_size,
             self.normalized_coord, flip=True)
@@ -228,6 +249,65 @@ class RawExport(torch.nn.Module):
         return boxes * scale, clss, scores
 
 
+SERVE_CAP = 2048  # candidates per image of the packed NMS (nms_common.h)
+
+
+class ServeExport(torch.nn.Module):
+    """The serving trace: one (H,W,3) uint8 device frame of any size ->
+    rthd::resize_frame -> network -> the decode of ``export`` (plain or flip
+    test) -> rthd::nms_pack with the confidence filter, the NMS mode and the
+    box rescale folded in -> ONE (1+N, 6) float32 tensor, N = stacks * topk:
+    row 0 is [count, 0, 0, 0, 0, 0], rows 1..count are [x1, y1, x2, y2,
+    score, class] in the frame's own pixels, the rest is zero.
+
+    Every op has a shape fixed by the configuration and none reads back to
+    the host, so a consumer may capture the whole forward into a graph
+    (tools/cpp_infer ``-g``, tools/serve_latency.py) and fetch the result
+    with one copy."""
+
+    def __init__(self, export, imsize, pretrained='imagenet'):
+        super().__init__()
+        from ..ops import hip
+        self.export = export
+        self.imsize = int(imsize)
+        self.mode = NMS_MODES.index(export.nms)
+        self.register_buffer(
+            'table', hip._norm_table(torch.device('cuda',
+                                                  torch.cuda.current_device()),
+                                     pretrained, torch.float32).clone())
+
+    def forward(self, frame):
+        image, scale = torch.ops.rthd.resize_frame(frame, self.imsize,
+                                                   self.table)
+        b, c, s = self.export.decode_native(image)
+        n = b.shape[0] * b.shape[1]
+        if n > SERVE_CAP:
+            raise ValueError(
+                'serving export: num_stack * topk = %d candidates exceed '
+                'the packed NMS limit of %d' % (n, SERVE_CAP))
+        e = self.export
+        # soft mode: sigma 0.5, drop at conf_th, as Export and Prediction
+        packed = torch.ops.rthd.nms_pack(
+            b.reshape(1, n, 4), c.reshape(1, n), s.reshape(1, n), scale,
+            self.mode, float(e.nms_th), 0.5, float(e.conf_th),
+            float(e.conf_th))
+        return packed[0]
+
+
+def build_serve_module(args, network, imsize):
+    """``ServeExport`` over ``build_export_module`` for the parsed flags."""
+    n = args.num_stack * args.topk
+    if n > SERVE_CAP:
+        raise ValueError(
+            '--serve: --num-stack * --topk = %d candidates exceed the packed '
+            'NMS limit of %d; lower --topk' % (n, SERVE_CAP))
+    if not torch.cuda.is_available():
+        raise RuntimeError('--serve needs a GPU and the kernel extension')
+    _backend.require_ext()
+    return ServeExport(build_export_module(args, network), imsize,
+                       args.pretrained)
+
+
 def build_export_module(args, network):
     return Export(
         network=network, topk=args.topk, scale_factor=args.scale_factor,
@@ -237,8 +317,24 @@ def build_export_module(args, network):
         flip_test=getattr(args, 'flip_test', False))
 
 
+def _trace_contexts(infer_dtype):
+    """The contexts a GPU trace of ``infer_dtype`` runs under: the amp
+    contexts of --infer-dtype, with torch.autocast's weight cache off (the
+    tracer must see every cast autocast inserts as an explicit op of this
+    trace, not a tensor cached by the warm-up call)."""
+    import contextlib
+    from .. import amp
+    stack = contextlib.ExitStack()
+    stack.enter_context(amp.infer_context(infer_dtype))
+    if infer_dtype != 'fp32':
+        stack.enter_context(torch.autocast(
+            device_type='cuda', dtype=torch.bfloat16, cache_enabled=False))
+    return stack
+
+
 def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,
-                 native=True, raw_input=False, pretrained='imagenet'):
+                 native=True, raw_input=False, pretrained='imagenet',
+                 infer_dtype='fp32', serve=None):
     """Trace and save cpu (and, if available, gpu) TorchScript models.
 
     The CPU trace records plain torch-ROCm eager ops — self-contained and
@@ -254,8 +350,20 @@ def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,
     native GPU trace behind ``RawExport``: it takes the raw uint8 frame and
     normalises with the ``pretrained`` scheme. The other files are the same
     with and without it.
+
+    ``infer_dtype`` 'bf16' / 'fp8' traces every GPU file under
+    ``amp.autocast`` (plus ``amp.fp8_autocast``) and saves it with a
+    ``_bf16`` / ``_fp8`` suffix before ``.pth``, next to (never over) an
+    fp32 export; the bf16 / e4m3 packed weights and the casts are part of
+    the trace, so the consumer needs no autocast state. The CPU trace is
+    always fp32. ``serve`` (a ``ServeExport``) additionally saves
+    jit_traced_model_gpu_serve<suffix>.pth.
     """
     import os
+    from ..config import INFER_DTYPES
+    if infer_dtype not in INFER_DTYPES:
+        raise ValueError('infer_dtype must be one of %s, got %r'
+                         % (', '.join(INFER_DTYPES), infer_dtype))
     os.makedirs(save_dir, exist_ok=True)
     predictor.eval()
     paths = {}
@@ -270,24 +378,33 @@ def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,
 
     if do_gpu is None:
         do_gpu = torch.cuda.is_available()
+    if not do_gpu and (infer_dtype != 'fp32' or serve is not None):
+        raise RuntimeError('infer_dtype %s / the serving export need a GPU'
+                           % infer_dtype)
     if do_gpu:
         if os.environ.get('RTHD_EXPORT_EAGER'):
             native = False
+        if not native and (infer_dtype != 'fp32' or serve is not None):
+            raise RuntimeError('bf16 / fp8 and the serving export record '
+                               'the native rthd ops: no eager variant')
+        suffix = '' if infer_dtype == 'fp32' else '_' + infer_dtype
         prev = os.environ.get('RTHD_EAGER_GPU')
         if not native:
             os.environ['RTHD_EAGER_GPU'] = '1'
         try:
             xg = torch.randn(1, 3, imsize, imsize, device='cuda')
             predictor = predictor.cuda()
-            with torch.no_grad():
+            with torch.no_grad(), _trace_contexts(infer_dtype):
                 if native:
                     # warm the conv inference caches first: the trace then
                     # bakes the FROZEN packed-weight/scale/shift tensors as
                     # constants (exact replay); a cold-cache trace records
-                    # the fold chain and was measured to misreplay.
+                    # the fold chain and was measured to misreplay. Under
+                    # the same contexts, so the frozen tensors are those of
+                    # infer_dtype.
                     predictor(xg)
                 traced_gpu = torch.jit.trace(predictor, xg)
-            p = os.path.join(save_dir, 'jit_traced_model_gpu.pth')
+            p = os.path.join(save_dir, 'jit_traced_model_gpu%s.pth' % suffix)
             torch.jit.save(traced_gpu, p)
             paths['gpu'] = p
             print('Model saved at gpu (%s ops): %s'
@@ -299,13 +416,30 @@ def export_model(predictor, save_dir='.', imsize=512, do_gpu=None,
                 raw = RawExport(predictor, imsize, pretrained).cuda().eval()
                 frame = torch.randint(0, 256, (imsize, imsize, 3),
                                       dtype=torch.uint8, device='cuda')
-                with torch.no_grad():
+                with torch.no_grad(), _trace_contexts(infer_dtype):
                     traced_raw = torch.jit.trace(raw, frame)
-                p = os.path.join(save_dir, 'jit_traced_model_gpu_raw.pth')
+                p = os.path.join(save_dir,
+                                 'jit_traced_model_gpu_raw%s.pth' % suffix)
                 torch.jit.save(traced_raw, p)
                 paths['gpu_raw'] = p
                 print('Raw-input model saved at gpu: %s (takes a (H,W,3) '
                       'uint8 frame; needs the kernel extension to load)' % p)
+            if serve is not None:
+                serve = serve.cuda().eval()
+                frame = torch.randint(0, 256, (imsize, imsize, 3),
+                                      dtype=torch.uint8, device='cuda')
+                with torch.no_grad(), _trace_contexts(infer_dtype):
+                    # its Export may be another module than ``predictor``
+                    # (or run the flip-test batch of two): warm it as well
+                    serve(frame)
+                    traced_serve = torch.jit.trace(serve, frame)
+                p = os.path.join(save_dir,
+                                 'jit_traced_model_gpu_serve%s.pth' % suffix)
+                torch.jit.save(traced_serve, p)
+                paths['gpu_serve'] = p
+                print('Serving model saved at gpu: %s (takes a (H,W,3) '
+                      'uint8 frame, returns packed (1+N, 6) detections; '
+                      'needs the kernel extension to load)' % p)
         finally:
             if prev is None:
                 os.environ.pop('RTHD_EAGER_GPU', None)

@@ -90,6 +90,21 @@ def soft_nms_batched(boxes, scores, sigma, score_th, conf_th):
     return eager.soft_nms_batched(boxes, scores, sigma, score_th, conf_th)
 
 
+def nms_pack(boxes, classes, scores, box_scale=None, mode=0, iou=0.5,
+             sigma=0.5, score_th=0.001, conf=0.0):
+    # either NMS mode (0 greedy, 1 Gaussian soft) with a fixed-shape packed
+    # result (B, 1+N, 6): one launch and no host sync on GPU (capturable)
+    if _hip(boxes):
+        from . import hip
+        return hip.nms_pack(boxes, classes, scores, box_scale, mode, iou,
+                            sigma, score_th, conf)
+    return eager.nms_pack(boxes, classes, scores, box_scale, mode, iou,
+                          sigma, score_th, conf)
+
+
+unpack_detections = eager.unpack_detections
+
+
 def resize_images(img_u8, sizes, T, pretrained=None, dtype=torch.float32):
     # --device-preprocess: Pillow-exact resize (+ normalise) of raw frames
     from . import functional

@@ -57,6 +57,11 @@ std::vector<torch::Tensor> soft_nms_batched(torch::Tensor boxes,
                                             torch::Tensor scores,
                                             double sigma, double score_th,
                                             double conf_th);
+torch::Tensor nms_pack(torch::Tensor boxes, torch::Tensor classes,
+                       torch::Tensor scores,
+                       c10::optional<torch::Tensor> box_scale, int64_t mode,
+                       double iou, double sigma, double score_th,
+                       double conf);
 
 torch::Tensor pack_weights(torch::Tensor w, bool swap, bool to_bf16);
 std::vector<torch::Tensor> pack_weights_pair(torch::Tensor w,
@@ -179,6 +184,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nms_batched", &rthd::nms_batched);
   m.def("soft_nms", &rthd::soft_nms_fwd);
   m.def("soft_nms_batched", &rthd::soft_nms_batched);
+  m.def("nms_pack", &rthd::nms_pack, py::arg("boxes"), py::arg("classes"),
+        py::arg("scores"), py::arg("box_scale") = py::none(),
+        py::arg("mode") = 0, py::arg("iou") = 0.5, py::arg("sigma") = 0.5,
+        py::arg("score_th") = 0.001, py::arg("conf") = 0.0);
   m.def("pack_weights",&rthd::pack_weights);
   m.def("pack_weights_pair", &rthd::pack_weights_pair);
   m.def("pack_weights_fp8", &rthd::pack_weights_fp8);
@@ -298,6 +307,9 @@ TORCH_LIBRARY(rthd, m) {
         "float score_th) -> (Tensor, Tensor)");
   m.def("soft_nms_batched(Tensor boxes, Tensor scores, float sigma, "
         "float score_th, float conf) -> (Tensor, Tensor, Tensor)");
+  m.def("nms_pack(Tensor boxes, Tensor classes, Tensor scores, "
+        "Tensor? box_scale, int mode, float iou, float sigma, "
+        "float score_th, float conf) -> Tensor");
   m.def("decode(Tensor hm, Tensor off, Tensor wh, int scale_factor, "
         "int topk, int pool_size, bool normalized) "
         "-> (Tensor, Tensor, Tensor)");
@@ -323,6 +335,7 @@ TORCH_LIBRARY_IMPL(rthd, CUDA, m) {
   m.impl("nms_batched", rthd::nms_batched_op);
   m.impl("soft_nms", rthd::soft_nms_op);
   m.impl("soft_nms_batched", rthd::soft_nms_batched_op);
+  m.impl("nms_pack", rthd::nms_pack);
   m.impl("decode", rthd::decode_op);
   m.impl("decode_logits", rthd::decode_logits_op);
   m.impl("stem_im2col", rthd::stem_im2col);

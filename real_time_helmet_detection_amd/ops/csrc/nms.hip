@@ -26,17 +26,23 @@ namespace rthd {
 // grid.x = image index (batched form; the single-image entry uses B=1).
 // conf: candidates with score < conf are neither suppressors nor output
 // (equivalent to filtering before NMS — they sort to the tail).
+// PACK: the packed emit of nms_pack (nms_common.h) replaces the index list;
+// out_idx / out_count are then unused (null) and LDS holds W more words.
+template <bool PACK>
 __global__ void nms_kernel(const float* __restrict__ boxes,  // (B,N,4)
                            const float* __restrict__ scores, // (B,N)
                            int* __restrict__ out_idx,        // (B,N)
                            int* __restrict__ out_count,      // (B,)
                            unsigned long long* __restrict__ mask_gb,
-                           int N, int P, int W, float thr, float conf) {
+                           int N, int P, int W, float thr, float conf,
+                           NmsPack pk) {
   const int bimg = blockIdx.x;
   boxes += (int64_t)bimg * N * 4;
   scores += (int64_t)bimg * N;
-  out_idx += (int64_t)bimg * N;
-  out_count += bimg;
+  if (!PACK) {
+    out_idx += (int64_t)bimg * N;
+    out_count += bimg;
+  }
   unsigned long long* mask_g =
       mask_gb ? mask_gb + (int64_t)bimg * N * W : nullptr;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -128,25 +134,73 @@ __global__ void nms_kernel(const float* __restrict__ boxes,  // (B,N,4)
   }
   __syncthreads();
 
-  if (threadIdx.x == 0) {
-    int k = 0;
-    for (int i = 0; i < N && ss[i] >= conf; ++i)
-      if (((rem[i >> 6] >> (i & 63)) & 1ull) == 0ull)
-        out_idx[k++] = sidx[i];
-    *out_count = k;
+  if (!PACK) {
+    if (threadIdx.x == 0) {
+      int k = 0;
+      for (int i = 0; i < N && ss[i] >= conf; ++i)
+        if (((rem[i >> 6] >> (i & 63)) & 1ull) == 0ull)
+          out_idx[k++] = sidx[i];
+      *out_count = k;
+    }
+    return;
   }
+
+  // ---- packed emit: parallel compaction of the survivors ----
+  // The serial loop above emits sorted position i iff every position <= i
+  // has score >= conf and i's bit of rem is clear. Per 64-candidate word:
+  // ballot the conf test, cut it at its first failure, clear the suppressed
+  // bits; a survivor's output slot is the popcount of the words before it
+  // plus that of the lower bits of its own word. A wave owns whole words
+  // (blockDim is a multiple of 64) and meets in the ballot only; the rest
+  // is ordered by the block barrier, not by wave lockstep.
+  unsigned long long* kw = const_cast<unsigned long long*>(rem) + W;
+  int* kfull = reinterpret_cast<int*>(kw + W);
+  for (int w = threadIdx.x >> 6; w < W; w += blockDim.x >> 6) {
+    const int i = w * 64 + (threadIdx.x & 63);
+    const unsigned long long ok = __ballot(i < N && ss[i] >= conf);
+    // bits below the first failing one (all 64 when none fails)
+    const unsigned long long lead =
+        ~ok == 0ull ? ~0ull : ((1ull << __builtin_ctzll(~ok)) - 1ull);
+    if ((threadIdx.x & 63) == 0) {
+      kw[w] = lead & ~rem[w];
+      kfull[w] = ~ok == 0ull;
+    }
+  }
+  __syncthreads();
+  // a word with a failing candidate ends the list: the words after it emit
+  // nothing. (The last word of an all-pass image is cut at N by the ballot.)
+  int total = 0;   // survivors of the whole image
+  int wend = W;    // first word past the list
+  for (int w = 0; w < W; ++w) {
+    total += __popcll(kw[w]);
+    if (!kfull[w]) { wend = w + 1; break; }
+  }
+  for (int i = threadIdx.x; i < N; i += blockDim.x) {
+    const int w = i >> 6, l = i & 63;
+    if (w >= wend) break;
+    const unsigned long long m = kw[w];
+    if (((m >> l) & 1ull) == 0ull) continue;
+    int k = __popcll(m & ((1ull << l) - 1ull));
+    for (int v = 0; v < w; ++v) k += __popcll(kw[v]);
+    nms_pack_record(pk, bimg, N, k, sidx[i], sx1[i], sy1[i], sx2[i], sy2[i],
+                    ss[i]);
+  }
+  nms_pack_finish(pk, bimg, N, total, threadIdx.x, blockDim.x);
 }
 
 // shared launch logic for the single-image and batched entries
+template <bool PACK>
 static void launch_nms(const float* pb, const float* psc, int* pidx,
                        int* pcnt, int B, int N, float thr, float conf,
-                       const torch::TensorOptions& opt) {
+                       const torch::TensorOptions& opt,
+                       NmsPack pk = NmsPack{nullptr, nullptr, nullptr, 0}) {
   int P = 64;
   while (P < N) P <<= 1;
   const int W = (int)cdiv(N, 64);
   const bool lds_mask = N <= 1024;  // [N][W] mask fits beside the arrays
   size_t lds = (size_t)P * 24 + (size_t)W * 8;
   if (lds_mask) lds += (size_t)N * W * 8;
+  if (PACK) lds += (size_t)W * 12;  // kw (u64) + kfull (int) per word
   torch::Tensor mask_ws;
   unsigned long long* mg = nullptr;
   if (!lds_mask) {
@@ -157,14 +211,66 @@ static void launch_nms(const float* pb, const float* psc, int* pidx,
     static std::once_flag once;
     std::call_once(once, [] {
       (void)hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&nms_kernel),
+          reinterpret_cast<const void*>(&nms_kernel<PACK>),
           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
   }
   auto s = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(nms_kernel, dim3(B), dim3(256), lds, s,
-      pb, psc, pidx, pcnt, mg, N, P, W, thr, conf);
+  hipLaunchKernelGGL(nms_kernel<PACK>, dim3(B), dim3(256), lds, s,
+      pb, psc, pidx, pcnt, mg, N, P, W, thr, conf, pk);
   HIP_CHECK_LAST();
+}
+
+// soft_nms.hip: the PACK instantiation of soft_nms_kernel
+void launch_soft_nms_pack(const float* boxes, const float* scores, int B,
+                          int N, float sigma, float score_th, float conf,
+                          NmsPack pk);
+
+// Either NMS mode with a packed, fixed-shape result (layout: nms_common.h).
+// mode 0 selects what nms_batched selects (original scores), mode 1 what
+// soft_nms_batched selects (rescored scores). One launch that writes every
+// output element: no memset, no atomics, no host read, no allocation sized
+// by data — deterministic and legal under stream capture. count is exact as
+// a float because N <= NMS_CAP.
+torch::Tensor nms_pack(torch::Tensor boxes, torch::Tensor classes,
+                       torch::Tensor scores,
+                       c10::optional<torch::Tensor> box_scale, int64_t mode,
+                       double iou, double sigma, double score_th,
+                       double conf) {
+  TORCH_CHECK(boxes.is_cuda() && classes.is_cuda() && scores.is_cuda(),
+              "nms_pack: device tensors");
+  TORCH_CHECK(mode == 0 || mode == 1, "nms_pack: mode 0 (greedy) or 1 (soft)");
+  auto b = boxes.to(at::kFloat).contiguous();
+  auto sc = scores.to(at::kFloat).contiguous();
+  auto cl = classes.to(at::kLong).contiguous();
+  TORCH_CHECK(b.dim() == 3 && b.size(2) == 4 && sc.dim() == 2 &&
+              cl.dim() == 2 && b.size(0) == sc.size(0) &&
+              b.size(1) == sc.size(1) && cl.size(0) == sc.size(0) &&
+              cl.size(1) == sc.size(1),
+              "nms_pack: (B,N,4)/(B,N)/(B,N)");
+  const int B = b.size(0), N = b.size(1);
+  TORCH_CHECK(N <= NMS_CAP, "nms_pack: N > cap (", N, " > ", NMS_CAP, ")");
+  NmsPack pk{cl.data_ptr<int64_t>(), nullptr, nullptr, 0};
+  torch::Tensor bs;
+  if (box_scale.has_value() && box_scale->defined()) {
+    bs = box_scale->to(at::kFloat).contiguous();
+    TORCH_CHECK(bs.is_cuda() &&
+                ((bs.dim() == 1 && bs.size(0) == 4) ||
+                 (bs.dim() == 2 && bs.size(0) == B && bs.size(1) == 4)),
+                "nms_pack: box_scale must be (4,) or (B,4) on the device");
+    pk.scale = bs.data_ptr<float>();
+    pk.scale_stride = bs.dim() == 2 ? 4 : 0;
+  }
+  if (N == 0 || B == 0) return torch::zeros({B, 1, NMS_REC}, b.options());
+  auto out = torch::empty({B, 1 + N, NMS_REC}, b.options());
+  pk.out = out.data_ptr<float>();
+  if (mode == 0)
+    launch_nms<true>(b.data_ptr<float>(), sc.data_ptr<float>(), nullptr,
+                     nullptr, B, N, (float)iou, (float)conf, b.options(), pk);
+  else
+    launch_soft_nms_pack(b.data_ptr<float>(), sc.data_ptr<float>(), B, N,
+                         (float)sigma, (float)score_th, (float)conf, pk);
+  return out;
 }
 
 // batched: one kernel, one later host sync for ALL images (the per-image
@@ -184,9 +290,9 @@ std::vector<torch::Tensor> nms_batched(torch::Tensor boxes,
                               b.options().dtype(at::kInt));
   auto out_count = torch::zeros({B}, b.options().dtype(at::kInt));
   if (N == 0) return {out_idx, out_count};
-  launch_nms(b.data_ptr<float>(), sc.data_ptr<float>(),
-             out_idx.data_ptr<int>(), out_count.data_ptr<int>(), B, N,
-             (float)iou_threshold, (float)conf_th, b.options());
+  launch_nms<false>(b.data_ptr<float>(), sc.data_ptr<float>(),
+                    out_idx.data_ptr<int>(), out_count.data_ptr<int>(), B,
+                    N, (float)iou_threshold, (float)conf_th, b.options());
   return {out_idx, out_count};
 }
 
@@ -202,9 +308,9 @@ torch::Tensor nms_fwd(torch::Tensor boxes, torch::Tensor scores,
                               b.options().dtype(at::kInt));
   auto out_count = torch::zeros({1}, b.options().dtype(at::kInt));
   if (N == 0) return torch::empty({0}, b.options().dtype(at::kLong));
-  launch_nms(b.data_ptr<float>(), sc.data_ptr<float>(),
-             out_idx.data_ptr<int>(), out_count.data_ptr<int>(), 1, N,
-             (float)iou_threshold, -3.4e38f, b.options());
+  launch_nms<false>(b.data_ptr<float>(), sc.data_ptr<float>(),
+                    out_idx.data_ptr<int>(), out_count.data_ptr<int>(), 1,
+                    N, (float)iou_threshold, -3.4e38f, b.options());
   const int k = out_count.item<int>();  // host sync: result used on host
   return out_idx.narrow(0, 0, k).to(at::kLong);
 }

@@ -79,14 +79,16 @@ DEV_INLINE unsigned long long snms_key(float s, int p) {
   return ((unsigned long long)f2ord(s) << 32) | (0xffffffffu - (unsigned)p);
 }
 
-// grid.x = image, block = one wave.
+// grid.x = image, block = one wave. PACK: the packed emit of nms_pack
+// (nms_common.h) replaces the three output arrays, which are then null.
+template <bool PACK>
 __global__ __launch_bounds__(64) void soft_nms_kernel(
     const float* __restrict__ boxes,   // (B,N,4)
     const float* __restrict__ scores,  // (B,N)
     int* __restrict__ out_idx,         // (B,N) zero-filled
     float* __restrict__ out_scores,    // (B,N) zero-filled
     int* __restrict__ out_count,       // (B,)
-    int N, float sigma, float score_th, float conf) {
+    int N, float sigma, float score_th, float conf, NmsPack pk) {
   __shared__ float sx1[NMS_CAP], sy1[NMS_CAP], sx2[NMS_CAP], sy2[NMS_CAP];
   __shared__ float ss[NMS_CAP];  // live score, NaN once selected or dropped
   __shared__ int sorig[NMS_CAP];
@@ -96,8 +98,10 @@ __global__ __launch_bounds__(64) void soft_nms_kernel(
   const float4* b4 =
       reinterpret_cast<const float4*>(boxes + (int64_t)bimg * N * 4);
   scores += (int64_t)bimg * N;
-  out_idx += (int64_t)bimg * N;
-  out_scores += (int64_t)bimg * N;
+  if (!PACK) {
+    out_idx += (int64_t)bimg * N;
+    out_scores += (int64_t)bimg * N;
+  }
 
   // ---- compact the candidates with score >= conf, order preserved ----
   int L = 0;
@@ -139,8 +143,13 @@ __global__ __launch_bounds__(64) void soft_nms_kernel(
     const float wx2 = sx2[pstar], wy2 = sy2[pstar];
     const float warea = box_area(wx1, wy1, wx2, wy2);
     if (lane == 0) {
-      out_idx[cnt] = sorig[pstar];
-      out_scores[cnt] = wscore;
+      if (PACK) {
+        nms_pack_record(pk, bimg, N, cnt, sorig[pstar], wx1, wy1, wx2, wy2,
+                        wscore);
+      } else {
+        out_idx[cnt] = sorig[pstar];
+        out_scores[cnt] = wscore;
+      }
     }
     ++cnt;
 
@@ -166,7 +175,23 @@ __global__ __launch_bounds__(64) void soft_nms_kernel(
     }
     best = wave_max_u64(best);
   }
+  if (PACK) {
+    // header and zero tail: with the records above, every element of the
+    // image's block has been stored once
+    nms_pack_finish(pk, bimg, N, cnt, lane, 64);
+    return;
+  }
   if (lane == 0) out_count[bimg] = cnt;
+}
+
+void launch_soft_nms_pack(const float* boxes, const float* scores, int B,
+                          int N, float sigma, float score_th, float conf,
+                          NmsPack pk) {
+  auto s = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(soft_nms_kernel<true>, dim3(B), dim3(64), 0, s, boxes,
+      scores, (int*)nullptr, (float*)nullptr, (int*)nullptr, N, sigma,
+      score_th, conf, pk);
+  HIP_CHECK_LAST();
 }
 
 static void launch_soft_nms(const torch::Tensor& b, const torch::Tensor& sc,
@@ -174,10 +199,11 @@ static void launch_soft_nms(const torch::Tensor& b, const torch::Tensor& sc,
                             torch::Tensor& cnt, int B, int N, double sigma,
                             double score_th, double conf_th) {
   auto s = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(soft_nms_kernel, dim3(B), dim3(64), 0, s,
+  hipLaunchKernelGGL(soft_nms_kernel<false>, dim3(B), dim3(64), 0, s,
       b.data_ptr<float>(), sc.data_ptr<float>(), idx.data_ptr<int>(),
       osc.data_ptr<float>(), cnt.data_ptr<int>(), N, (float)sigma,
-      (float)score_th, (float)conf_th);
+      (float)score_th, (float)conf_th,
+      NmsPack{nullptr, nullptr, nullptr, 0});
   HIP_CHECK_LAST();
 }
 

@@ -485,3 +485,58 @@ def soft_nms_batched(boxes, scores, sigma, score_th, conf_th):
         idx[i, :k] = sel[kept].to(torch.int32)
         out[i, :k] = rescored
     return idx, out, counts
+
+
+def nms_pack(boxes, classes, scores, box_scale=None, mode=0, iou=0.5,
+             sigma=0.5, score_th=0.001, conf=0.0):
+    """Eager twin (and oracle) of the packed-emit NMS kernel: either NMS mode
+    with a fixed-shape result. boxes (B,N,4), classes (B,N), scores (B,N) ->
+    (B, 1+N, 6) float32: row 0 of an image is [count, 0, 0, 0, 0, 0], rows
+    1..count are [x1, y1, x2, y2, score, class] in selection order, the rest
+    is zero. ``mode`` 0 is ``nms_batched`` (original scores), 1 is
+    ``soft_nms_batched`` (rescored scores). ``box_scale`` (4,) or (B,4)
+    multiplies the emitted boxes (x, y, x, y)."""
+    if mode not in (0, 1):
+        raise ValueError('nms_pack: mode 0 (greedy) or 1 (soft), got %r'
+                         % (mode,))
+    B, N = scores.shape
+    boxes = boxes.float()
+    scores = scores.float()
+    out = torch.zeros(B, 1 + N, 6, dtype=torch.float32, device=boxes.device)
+    if N == 0 or B == 0:
+        return out
+    if mode == 0:
+        idx, counts = nms_batched(boxes, scores, iou, conf)
+        kept_scores = None
+    else:
+        idx, kept_scores, counts = soft_nms_batched(boxes, scores, sigma,
+                                                    score_th, conf)
+    if box_scale is not None:
+        box_scale = box_scale.float().reshape(-1, 4).expand(B, 4)
+    for i, k in enumerate(counts.tolist()):
+        sel = idx[i, :k].long()
+        b = boxes[i][sel]
+        if box_scale is not None:
+            b = b * box_scale[i]
+        out[i, 0, 0] = k
+        out[i, 1:1 + k, :4] = b
+        out[i, 1:1 + k, 4] = scores[i][sel] if kept_scores is None \
+            else kept_scores[i, :k]
+        out[i, 1:1 + k, 5] = classes[i][sel].float()
+    return out
+
+
+def unpack_detections(packed):
+    """A packed (B, 1+N, 6) or single-image (1+N, 6) ``nms_pack`` result, on
+    any device -> the per-image lists (boxes (K,4), classes int64 (K),
+    scores (K)) that ``postprocess`` returns. One host read of the counts."""
+    if packed.dim() == 2:
+        packed = packed.unsqueeze(0)
+    counts = packed[:, 0, 0].to(torch.int64).cpu().tolist()
+    box_lst, cls_lst, score_lst = [], [], []
+    for i, k in enumerate(counts):
+        rows = packed[i, 1:1 + k]
+        box_lst.append(rows[:, :4])
+        cls_lst.append(rows[:, 5].to(torch.int64))
+        score_lst.append(rows[:, 4])
+    return box_lst, cls_lst, score_lst

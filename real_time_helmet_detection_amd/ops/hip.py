@@ -387,7 +387,10 @@ def _conv_infer(x, conv, bn, act_code, skip, kh, kw, stride, pad, is_stem):
     per-call pack + fold, and a trace bakes the frozen tensors as
     constants."""
     ops = _ops()
-    bf16 = _bf16_mode(x) and (is_stem or x.shape[1] % 8 == 0)
+    # bool(): under torch.jit.trace a shape is a traced value, and the cache
+    # key below must compare as plain python (a traced `==` lands in the
+    # graph)
+    bf16 = bool(_bf16_mode(x) and (is_stem or x.shape[1] % 8 == 0))
     dtype = torch.bfloat16 if bf16 else torch.float32
     xc = x.to(dtype).contiguous(memory_format=torch.channels_last)
     skc = None
@@ -854,3 +857,17 @@ def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, score_th=0.001):
     keep, rescored = _C().soft_nms(boxes, scores, float(sigma),
                                    float(score_th))
     return keep, rescored
+
+
+def nms_pack(boxes, classes, scores, box_scale=None, mode=0, iou=0.5,
+             sigma=0.5, score_th=0.001, conf=0.0):
+    """Either NMS mode with the packed, fixed-shape emit (ops.eager.nms_pack
+    has the layout): ONE launch, no host sync, legal under stream capture.
+    Goes through the dispatcher op so a trace records it."""
+    if boxes.shape[1] > _NMS_CAP:
+        from .eager import nms_pack as eager_np
+        return eager_np(boxes, classes, scores, box_scale, mode, iou, sigma,
+                        score_th, conf)
+    return _ops().nms_pack(boxes, classes, scores, box_scale, int(mode),
+                           float(iou), float(sigma), float(score_th),
+                           float(conf))

@@ -24,12 +24,30 @@
 // normalises it on the device bit-identically to the Python path, and the
 // boxes are printed in the source image's pixels. GPU only; -s is unused
 // (the size is baked into the trace).
+//
+//   ./helmet_infer [-g] -m jit_traced_model_gpu_serve[_bf16|_fp8].pth \
+//       -k <_C*.so> -i image.ppm
+//
+// A serving model (export.py --serve) is recognised by its output: ONE
+// packed (1+N, 6) float tensor instead of a tuple — row 0 [count, 0...],
+// rows 1..count [x1 y1 x2 y2 score class] in the frame's pixels. It takes
+// the raw frame like -r. Each iteration copies the frame from pinned host
+// memory into a static device input, runs the model, copies the packed
+// tensor back to pinned host memory and synchronises; the FPS includes both
+// copies. Plain, the model runs by forward. With -g the forward is captured
+// once into a device graph (three warm-up forwards on a side stream first,
+// so the conv variant choice and the TorchScript executor have settled) and
+// replayed per iteration. If the capture throws, the app
+// reports it and exits non-zero.
 // When the traced GPU model embeds the native gfx950 ops (torch.ops.rthd.*,
 // the default export.py GPU trace), pass the kernel extension with
 // -k <path to real_time_helmet_detection_amd/ops/_C*.so>; it is dlopen'd
 // before torch::jit::load so the rthd:: custom ops resolve.
 #include <torch/script.h>
 #include <ATen/hip/HIPContext.h>
+#include <ATen/hip/HIPGraph.h>
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
+#include <c10/core/StreamGuard.h>
 #include <dlfcn.h>
 
 #include <chrono>
@@ -81,12 +99,96 @@ static torch::Tensor load_image(const std::string& path, int imsize) {
   return img;
 }
 
+static const char* kNames[] = {"hat", "person"};
+
+// detections of a packed (1+N, 6) host tensor
+static void print_packed(const torch::Tensor& packed) {
+  auto p = packed.contiguous();
+  const float* d = p.data_ptr<float>();
+  const int64_t n = p.size(0) - 1;
+  const int64_t count = std::min<int64_t>(std::max<int64_t>((int64_t)d[0], 0),
+                                          n);
+  const int nshow = (int)std::min<int64_t>(count, 20);
+  printf("%lld detections (showing %d)\n", (long long)count, nshow);
+  for (int i = 0; i < nshow; ++i) {
+    const float* r = d + (int64_t)(1 + i) * 6;
+    const int cls = (int)r[5];
+    printf("det %2d: %-7s score %.3f box [%7.1f %7.1f %7.1f %7.1f]\n", i,
+           cls >= 0 && cls < 2 ? kNames[cls] : "?", r[4], r[0], r[1], r[2],
+           r[3]);
+  }
+}
+
+// serving model: frame is the (H,W,3) uint8 host tensor
+static int run_serving(torch::jit::script::Module& model,
+                       const torch::Tensor& frame, torch::Device device,
+                       int iters, bool graph_mode) {
+  auto host_in = frame.pin_memory();
+  auto static_in = torch::empty_like(frame, frame.options().device(device));
+  // everything below runs on a stream of our own: a capture may not use the
+  // default stream
+  // (the generic guard and the device-wide synchronise: the HIP-specific
+  // ones are inline calls into the HIP runtime, which this app does not link
+  // — see CMakeLists.txt; nothing else runs on the device here)
+  auto stream = c10::hip::getStreamFromPoolMasqueradingAsCUDA();
+  c10::StreamGuard guard(stream.unwrap());
+  static_in.copy_(host_in, /*non_blocking=*/true);
+
+  torch::Tensor out;
+  for (int i = 0; i < 3; ++i) out = model.forward({static_in}).toTensor();
+  at::hip::device_synchronize();
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == 6 &&
+                  out.scalar_type() == torch::kFloat32,
+              "serving model: expected a packed (1+N, 6) float tensor");
+
+  at::cuda::CUDAGraph graph;
+  if (graph_mode) {
+    try {
+      graph.capture_begin();
+      out = model.forward({static_in}).toTensor();
+      graph.capture_end();
+    } catch (const std::exception& e) {
+      std::cerr << "helmet_infer: graph capture failed: " << e.what() << "\n";
+      return 2;
+    }
+  }
+  auto host_out = torch::empty(
+      out.sizes(), out.options().device(torch::kCPU).pinned_memory(true));
+
+  auto step = [&]() {
+    static_in.copy_(host_in, /*non_blocking=*/true);
+    if (graph_mode)
+      graph.replay();
+    else
+      out = model.forward({static_in}).toTensor();
+    host_out.copy_(out, /*non_blocking=*/true);
+    at::hip::device_synchronize();
+  };
+  step();
+  print_packed(host_out);
+
+  for (int i = 0; i < 10; ++i) step();
+  auto t0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < iters; ++i) step();
+  auto t1 = std::chrono::steady_clock::now();
+  const double sec = std::chrono::duration<double>(t1 - t0).count();
+  printf("%d iters in %.3f s -> %.1f FPS, raw %lldx%lld frame, serving "
+         "model, %s (gpu)\n", iters, sec, iters / sec,
+         (long long)frame.size(1), (long long)frame.size(0),
+         graph_mode ? "graph replay, frame upload and result download "
+                      "included"
+                    : "plain forward, frame upload and result download "
+                      "included");
+  return 0;
+}
+
 static int run(int argc, char** argv) {
   std::string model_path, image_path, kernels_path;
   int iters = 100, imsize = 512;
-  bool raw = false;
+  bool raw = false, graph_mode = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "-r")) { raw = true; continue; }
+    if (!strcmp(argv[i], "-g")) { graph_mode = true; continue; }
     if (i >= argc - 1) break;  // every other flag takes a value
     if (!strcmp(argv[i], "-m")) model_path = argv[++i];
     else if (!strcmp(argv[i], "-i")) image_path = argv[++i];
@@ -97,7 +199,7 @@ static int run(int argc, char** argv) {
   if (model_path.empty() || image_path.empty()) {
     std::cerr << "usage: " << argv[0]
               << " -m model.pth -i image.ppm [-k rthd_ops.so] [-n iters]"
-                 " [-s imsize] [-r]\n";
+                 " [-s imsize] [-r] [-g]\n";
     return 1;
   }
   if (!kernels_path.empty()) {
@@ -116,18 +218,36 @@ static int run(int argc, char** argv) {
   torch::Device device(cuda ? torch::kCUDA : torch::kCPU);
   model.to(device);
 
-  if (raw && !cuda)
-    throw std::runtime_error("-r needs a GPU and a jit_traced_model_gpu_raw "
-                             "model");
+  // a serving model takes the raw frame too; its file name says so, its
+  // output (a tensor, no tuple) confirms it
+  const bool serve_name =
+      model_path.find("gpu_serve") != std::string::npos;
+  if ((raw || serve_name || graph_mode) && !cuda)
+    throw std::runtime_error("-r, -g and serving models need a GPU and a "
+                             "jit_traced_model_gpu_raw / _gpu_serve model");
+  torch::NoGradGuard ng;
+  if (serve_name) {
+    auto frame = read_ppm(image_path);
+    auto probe = model.forward({frame.to(device)});
+    if (probe.isTensor())
+      return run_serving(model, frame, device, iters, graph_mode);
+    throw std::runtime_error("model named gpu_serve returns no tensor");
+  }
+  if (graph_mode)
+    throw std::runtime_error("-g replays serving models only "
+                             "(jit_traced_model_gpu_serve*.pth)");
   auto img = raw ? read_ppm(image_path).to(device)
                  : load_image(image_path, imsize).to(device);
 
-  torch::NoGradGuard ng;
-  auto out = model.forward({img}).toTuple();
+  auto first = model.forward({img});
+  if (first.isTensor())
+    throw std::runtime_error("this model returns a packed tensor: it is a "
+                             "serving model, keep gpu_serve in its name");
+  auto out = first.toTuple();
   auto boxes = out->elements()[0].toTensor().cpu();
   auto clss = out->elements()[1].toTensor().cpu();
   auto scores = out->elements()[2].toTensor().cpu();
-  const char* names[] = {"hat", "person"};
+  const char* const* names = kNames;
   const int nshow = std::min<int64_t>(boxes.size(0), 20);
   printf("%lld detections (showing %d)\n", (long long)boxes.size(0), nshow);
   for (int i = 0; i < nshow; ++i) {
