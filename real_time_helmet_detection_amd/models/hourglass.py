@@ -164,8 +164,17 @@ class Residual(nn.Module):
 
     def forward(self, x):
         y1 = self.conv1(x)
-        s = x if isinstance(self.skip, nn.Identity) else self.skip(x)
         name = self.activation.name
+        sk, c2 = self.skip, self.conv2
+        if (name in FUSIBLE_ACTS and isinstance(sk, Convolution)
+                and isinstance(sk.bn, nn.BatchNorm2d)
+                and isinstance(c2.bn, nn.BatchNorm2d)
+                and sk.activation.name == 'Linear'):
+            # skip conv+BN: its BN is applied inside conv2's BN passes
+            return F2.conv_bn_act_skipconv(
+                y1, c2.convolution, c2.bn, name, self.training, x,
+                sk.convolution, sk.bn)
+        s = x if isinstance(self.skip, nn.Identity) else self.skip(x)
         if name in FUSIBLE_ACTS:
             # fuse skip-add + outer activation into conv2's epilogue
             return self.conv2(y1, skip=s, act_override=name)

@@ -127,7 +127,12 @@ int64_t wgrad_bf16_chunk_len(int64_t Cin, int64_t Cout, int64_t taps,
 std::vector<torch::Tensor> conv_fwd_stats(
     torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
     torch::Tensor shift, int64_t KH, int64_t KW, int64_t stride,
-    int64_t pad, int64_t Cout, int64_t act);
+    int64_t pad, int64_t Cout, int64_t act, int64_t halo_min_tiles);
+std::vector<torch::Tensor> conv_fwd_halo_stats(
+    torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
+    torch::Tensor shift, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
+    int64_t Cout, int64_t act, c10::optional<torch::Tensor> p1,
+    c10::optional<torch::Tensor> p2);
 std::vector<torch::Tensor> bn_stats_from_parts(
     torch::Tensor p1, torch::Tensor p2,
     c10::optional<torch::Tensor> running_mean,
@@ -146,6 +151,17 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
                                       torch::Tensor gamma, torch::Tensor beta,
                                       int64_t act,
                                       c10::optional<torch::Tensor> skip);
+torch::Tensor bn_act_fwd_dual(torch::Tensor x, torch::Tensor mean,
+                              torch::Tensor rstd, torch::Tensor gamma,
+                              torch::Tensor beta, torch::Tensor xs,
+                              torch::Tensor mean_s, torch::Tensor rstd_s,
+                              torch::Tensor gamma_s, torch::Tensor beta_s,
+                              int64_t act);
+std::vector<torch::Tensor> bn_act_bwd_dual(
+    torch::Tensor dy, torch::Tensor x, torch::Tensor mean,
+    torch::Tensor rstd, torch::Tensor gamma, torch::Tensor beta,
+    torch::Tensor xs, torch::Tensor mean_s, torch::Tensor rstd_s,
+    torch::Tensor gamma_s, torch::Tensor beta_s, int64_t act);
 torch::Tensor col_sum(torch::Tensor x);
 
 std::vector<torch::Tensor> encode_targets(torch::Tensor boxes,
@@ -212,7 +228,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride"), py::arg("pad"), py::arg("h"), py::arg("w"),
         py::arg("b"));
   m.def("wgrad_row_chunk_len", &rthd::wgrad_row_chunk_len);
-  m.def("conv_fwd_stats", &rthd::conv_fwd_stats);
+  m.def("conv_fwd_stats", &rthd::conv_fwd_stats, py::arg("x"),
+        py::arg("wpk"), py::arg("scale"), py::arg("shift"), py::arg("kh"),
+        py::arg("kw"), py::arg("stride"), py::arg("pad"), py::arg("cout"),
+        py::arg("act"), py::arg("halo_min_tiles") = -1);
+  m.def("conv_fwd_halo_stats", &rthd::conv_fwd_halo_stats, py::arg("x"),
+        py::arg("wpk"), py::arg("scale"), py::arg("shift"), py::arg("kh"),
+        py::arg("kw"), py::arg("stride"), py::arg("pad"), py::arg("cout"),
+        py::arg("act"), py::arg("p1") = py::none(),
+        py::arg("p2") = py::none());
   m.def("bn_stats_from_parts", &rthd::bn_stats_from_parts,
         py::arg("p1"), py::arg("p2"), py::arg("running_mean") = py::none(),
         py::arg("running_var") = py::none(), py::arg("momentum") = 0.1,
@@ -220,6 +244,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_stats", &rthd::bn_stats);
   m.def("bn_act_fwd", &rthd::bn_act_fwd, py::arg("x"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("act"), py::arg("skip") = py::none());
   m.def("bn_act_bwd", &rthd::bn_act_bwd, py::arg("dy"), py::arg("x"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("beta"), py::arg("act"), py::arg("skip") = py::none());
+  m.def("bn_act_fwd_dual", &rthd::bn_act_fwd_dual);
+  m.def("bn_act_bwd_dual", &rthd::bn_act_bwd_dual);
   m.def("col_sum", &rthd::col_sum);
   m.def("encode_targets", &rthd::encode_targets);
   m.def("normalize_u8", &rthd::normalize_u8);

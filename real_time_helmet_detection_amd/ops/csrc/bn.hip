@@ -20,6 +20,13 @@
 // parameters hoist out of the row loop. Requires octs = C/8 a power of two;
 // anything else falls back to the scalar generic path.
 //
+// Dual form (a Residual whose skip is conv+BN): y = act(bn(x) + bf16(bn_s(xs)))
+// in ONE forward pass and one reduce + one apply pass backward, in place of
+// the skip BN's own three kernels; the normalised skip s and its gradient
+// never reach memory. Both are rounded in registers exactly where their
+// stores rounded them, and every sum keeps its chunking, its stream walk and
+// its finish, so the results are bitwise those of the separate kernels.
+//
 // Layout of this file: each mapping (scalar, octet) has ONE reduce skeleton
 // and ONE apply shell; what a kernel computes is a small functor handed to
 // the skeleton as its first argument.
@@ -79,6 +86,52 @@ DEV_INLINE BnOct load_oct(const BnParams& p, int c0) {
   }
   return o;
 }
+
+// value of v after a store to T and a load back
+template <typename T> DEV_INLINE float round_as(float v);
+template <> DEV_INLINE float round_as<float>(float v) { return v; }
+template <> DEV_INLINE float round_as<bf16>(float v) { return b2f(f2b(v)); }
+
+// The skip tensor of the dual kernels, as the forward kernel of the same
+// mapping wrote it (Linear act): the scalar kernels use the unfolded
+// expression, the octet kernels the folded scale/shift one.
+template <typename T>
+DEV_INLINE float bn_skip_elem(float xs, float mu, float rsd, float gm,
+                              float bt) {
+  const float xh = (xs - mu) * rsd;
+  return round_as<T>(xh * gm + bt);
+}
+
+struct BnFold {
+  float sc[8], sh[8];
+};
+
+DEV_INLINE BnFold fold_oct(const BnParams& p, int c0) {
+  BnFold f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float g = p.gamma[c0 + e] * p.rstd[c0 + e];
+    f.sc[e] = g;
+    f.sh[e] = p.beta[c0 + e] - p.mean[c0 + e] * g;
+  }
+  return f;
+}
+
+DEV_INLINE float bn_skip_oct(float xs, float sc, float sh) {
+  return b2f(f2b(xs * sc + sh));
+}
+
+// number of column groups ("pairs" of sums) a reduce functor carries: the
+// dual functors say kPairs = 2 and see virtual columns [0, 2C), the second C
+// of them being the skip BN's
+template <typename F, typename = void>
+struct reduce_pairs {
+  static constexpr int value = 1;
+};
+template <typename F>
+struct reduce_pairs<F, std::void_t<decltype(F::kPairs)>> {
+  static constexpr int value = F::kPairs;
+};
 
 // fixed-order sum of the 4 sub-streams of a 64-channel x 4 block
 DEV_INLINE float sum4(const float* sh) {
@@ -143,6 +196,19 @@ struct ColSumRow8 {
   }
 };
 
+// column sums of two fp32 [rows][C] partial matrices at once (the conv
+// epilogue's sum and sumsq rows): s over a, ss over b
+struct PartsElem {
+  static constexpr bool kTwo = true;
+  const float *a, *b;
+  struct Ch {};
+  DEV_INLINE Ch channel(int) const { return {}; }
+  DEV_INLINE void add(const Ch&, int64_t i, float& s, float& ss) const {
+    s += a[i];
+    ss += b[i];
+  }
+};
+
 // a1 = sum dpre (d_beta), a2 = sum dpre*xhat (d_gamma)
 template <typename T, bool HAS_SKIP>
 struct BnBwdElem {
@@ -191,6 +257,99 @@ struct BnBwdRow8 {
           HAS_SKIP ? b2f(v.skip[e]) : 0.f, b2f(v.dy[e]), act);
       a1[e] += g.dpre;
       a2[e] += g.dpre * g.xh;
+    }
+  }
+};
+
+// The separate OCTET kernels leave three contractions to the compiler,
+// which fuses dy*act' into its consumers: sum dpre is fma(dy, act', a1), the
+// sum with xhat is fma(xhat, round(dy*act'), a2), and the apply's
+// dpre - s1/M is fma(dy, act', -s1/M). Inside the dual octet kernels the
+// same source text contracts differently (the selects and the extra use of
+// dpre are in the way), so there these three are written out. The scalar
+// dual kernels keep the plain source text, which compiles to what the
+// separate scalar kernels compute (tests/test_gpu_bn_dual.py holds both to
+// torch.equal).
+DEV_INLINE void dual_sums(bool second, const BnGrad& g, float dy, float sel,
+                          float xh_s, float dsk, float& a1, float& a2) {
+  a1 = __builtin_fmaf(second ? dsk : dy, second ? 1.f : sel, a1);
+  a2 = __builtin_fmaf(second ? xh_s : g.xh, second ? dsk : g.dpre, a2);
+}
+
+// Dual backward sums. Virtual column cv < C: the main BN's sums of column cv
+// (what BnBwd*<true> adds, with the skip recomputed); cv >= C: the skip
+// BN's sums of column cv - C over dskip = round(dpre) (what BnBwd*<false>
+// adds on the stored dskip, act Linear). A thread owns one virtual column
+// (octet) and walks the rows its twin in the separate kernels walks.
+template <typename T>
+struct BnBwdDualElem {
+  static constexpr bool kTwo = true;
+  static constexpr int kPairs = 2;
+  const T *dy, *x, *xs;
+  BnParams p, ps;
+  int act, C;
+  struct Ch {
+    float mu, rsd, gm, bt, mus, rsds, gms, bts;
+    bool second;
+  };
+  DEV_INLINE Ch channel(int cv) const {
+    const int c = cv % C;
+    return {p.mean[c], p.rstd[c], p.gamma[c], p.beta[c], ps.mean[c],
+            ps.rstd[c], ps.gamma[c], ps.beta[c], cv >= C};
+  }
+  DEV_INLINE void add(const Ch& ch, int64_t i, float& a1, float& a2) const {
+    const float xsv = ldf(&xs[i]);
+    const float dyv = ldf(&dy[i]);
+    const float sk = bn_skip_elem<T>(xsv, ch.mus, ch.rsds, ch.gms, ch.bts);
+    const BnGrad g = bn_grad<true>(ldf(&x[i]), ch.mu, ch.rsd, ch.gm, ch.bt,
+                                   sk, dyv, act);
+    const BnGrad gs = bn_grad<false>(xsv, ch.mus, ch.rsds, ch.gms, ch.bts,
+                                     0.f, round_as<T>(g.dpre), ACT_LINEAR);
+    const float d = ch.second ? gs.dpre : g.dpre;
+    const float xh = ch.second ? gs.xh : g.xh;
+    a1 += d;
+    a2 += d * xh;
+  }
+};
+
+struct BnBwdDualRow8 {
+  static constexpr bool kTwo = true;
+  static constexpr int kPairs = 2;
+  static constexpr int kTailRows = 8;
+  const bf16 *dy, *x, *xs;
+  BnParams p, ps;
+  int act, C;
+  struct Ch {
+    BnOct m, s;
+    BnFold f;
+    bool second;
+  };
+  struct Row {
+    bf16 x[8], dy[8], xs[8];
+  };
+  DEV_INLINE Ch channel(int cv0) const {
+    const int c0 = cv0 % C;
+    return {load_oct(p, c0), load_oct(ps, c0), fold_oct(ps, c0), cv0 >= C};
+  }
+  DEV_INLINE void load(Row& v, int64_t i) const {
+    ld8(v.x, x + i);
+    ld8(v.dy, dy + i);
+    ld8(v.xs, xs + i);
+  }
+  DEV_INLINE void add(const Ch& ch, const Row& v, float (&a1)[8],
+                      float (&a2)[8]) const {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xsv = b2f(v.xs[e]);
+      const float dyv = b2f(v.dy[e]);
+      const float sk = bn_skip_oct(xsv, ch.f.sc[e], ch.f.sh[e]);
+      const BnGrad g = bn_grad<true>(b2f(v.x[e]), ch.m.mu[e], ch.m.rsd[e],
+                                     ch.m.gm[e], ch.m.bt[e], sk, dyv, act);
+      const BnGrad gs = bn_grad<false>(xsv, ch.s.mu[e], ch.s.rsd[e],
+                                       ch.s.gm[e], ch.s.bt[e], 0.f,
+                                       b2f(f2b(g.dpre)), ACT_LINEAR);
+      dual_sums(ch.second, g, dyv, act_grad_by_sign(g.pre, act), gs.xh,
+                gs.dpre, a1[e], a2[e]);
     }
   }
 };
@@ -330,17 +489,20 @@ DEV_INLINE void ld_rowv(float (&v)[V], const float* p, unsigned off) {
   }
 }
 
-template <bool TWO, int U, int V>
+// NT: threads of the block; the slice is reduced by the first 256 (4
+// sub-streams of 64), the others only keep the barriers.
+template <bool TWO, int U, int V, int NT = 256>
 DEV_INLINE void ticket_reduce_slice(const float* p1, const float* p2,
                                     float* o1, float* o2, int k0, int k1,
                                     int c_lo, int c_hi, int C, float* sh) {
   // 32-bit element offsets (chunks * C <= 1024 * 2048) on the uniform row
   // bases: one offset register serves both sums
   const int sub = threadIdx.x >> 6;
+  const bool mine = NT == 256 || threadIdx.x < 256;
   for (int cb = c_lo; cb < c_hi; cb += 64 * V) {
     const int c = cb + (threadIdx.x & 63) * V;
     float a[V] = {}, b[V] = {};
-    if (c < c_hi) {
+    if (mine && c < c_hi) {
       // every round loads U rows before its first add, the last one too:
       // a row past the slice is loaded from row k instead and not added
       for (int k = k0 + sub; k < k1; k += 4 * U) {
@@ -365,10 +527,12 @@ DEV_INLINE void ticket_reduce_slice(const float* p1, const float* p2,
       }
     }
     // sum4 tiles: [sum][v][256]
+    if (mine) {
 #pragma unroll
-    for (int v = 0; v < V; ++v) {
-      sh[v * 256 + threadIdx.x] = a[v];
-      if (TWO) sh[(V + v) * 256 + threadIdx.x] = b[v];
+      for (int v = 0; v < V; ++v) {
+        sh[v * 256 + threadIdx.x] = a[v];
+        if (TWO) sh[(V + v) * 256 + threadIdx.x] = b[v];
+      }
     }
     __syncthreads();
     if (sub == 0 && c < c_hi) {
@@ -393,7 +557,7 @@ constexpr int kTicketLdsWide = 4 * 256 + 1;
 // nine adjacent words serialise on that one line (about 17 ns each)
 constexpr int kTicketStride = 32;
 
-template <bool TWO, int U, bool WIDE>
+template <bool TWO, int U, bool WIDE, int NT = 256>
 DEV_INLINE void ticket_finish(const BnTicket& t, const float* p1,
                               const float* p2, int c_lo, int c_hi, int C,
                               float* sh) {
@@ -411,16 +575,17 @@ DEV_INLINE void ticket_finish(const BnTicket& t, const float* p1,
     float* o1 = t.st1 + (int64_t)s * C;
     float* o2 = t.st2 + (int64_t)s * C;
     if (WIDE && C % 128 == 0)
-      ticket_reduce_slice<TWO, U, 2>(p1, p2, o1, o2, k0, k1, c_lo, c_hi, C,
-                                     sh);
+      ticket_reduce_slice<TWO, U, 2, NT>(p1, p2, o1, o2, k0, k1, c_lo, c_hi,
+                                         C, sh);
     else
-      ticket_reduce_slice<TWO, U, 1>(p1, p2, o1, o2, k0, k1, c_lo, c_hi, C,
-                                     sh);
+      ticket_reduce_slice<TWO, U, 1, NT>(p1, p2, o1, o2, k0, k1, c_lo, c_hi,
+                                         C, sh);
     f1 = t.st1;
     f2 = t.st2;
     fk = kTicketSlices;
   }
   if (!ticket_is_last(cnt + kTicketSlices * kTicketStride, fk, flag)) return;
+  if (NT != 256 && threadIdx.x >= 256) return;
   for (int c = c_lo + threadIdx.x; c < c_hi; c += 256)
     reduce_final_channel<TWO>(f1, f2, t.o1, t.o2, fk, C, c, t.fin);
 }
@@ -430,11 +595,16 @@ DEV_INLINE void ticket_finish(const BnTicket& t, const float* p1,
 // it owns and stores one partial row p1[y][C] (and p2[y][C]); with a ticket
 // the launch also finishes the reduction (above).
 
-// scalar, any C: block = 64 channels x 4 row sub-streams, grid (C/64, chunks)
+// scalar, any C: block = 64 channels x 4 row sub-streams, grid (C/64, chunks).
+// With a kPairs = 2 functor the columns are the 2C virtual ones (partial
+// rows are 2C wide; the data rows stay C wide).
 template <typename F>
 __global__ void reduce_part_kernel(const F f, float* p1, float* p2,
-                                   int64_t M, int C, const BnTicket tk) {
+                                   int64_t M, int Cd, const BnTicket tk) {
+  constexpr int NP = reduce_pairs<F>::value;
+  const int C = Cd * NP;  // columns of the partial rows
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int cd = NP == 1 ? c : c % Cd;  // column of the data rows
   const int sub = threadIdx.x >> 6;
   const bool live = c < C;
   const int64_t rows_per_chunk = (M + gridDim.y - 1) / gridDim.y;
@@ -443,7 +613,7 @@ __global__ void reduce_part_kernel(const F f, float* p1, float* p2,
   float a1 = 0.f, a2 = 0.f;
   if (live) {
     const typename F::Ch ch = f.channel(c);
-    for (int64_t r = r0 + sub; r < r1; r += 4) f.add(ch, r * C + c, a1, a2);
+    for (int64_t r = r0 + sub; r < r1; r += 4) f.add(ch, r * Cd + cd, a1, a2);
   }
   // one LDS object: the two sum4 tiles, and the ticket tail's flag word
   __shared__ float sh[kTicketLds];
@@ -464,14 +634,19 @@ __global__ void reduce_part_kernel(const F f, float* p1, float* p2,
 // bf16 octets, C = 8*2^k: block = octs x streams threads, grid (1, chunks),
 // LDS halving tree over the streams. UNROLL rows are loaded before any is
 // consumed (independent 16-B loads in flight).
+// A kPairs = 2 functor runs on 512 threads over the 2C virtual columns: the
+// streams and their row walk are those of the 256-thread launch at C.
 template <int UNROLL, typename F>
 __global__ void reduce8_part_kernel(const F f, float* p1, float* p2,
-                                    int64_t M, int C, const BnTicket tk) {
+                                    int64_t M, int Cd, const BnTicket tk) {
+  constexpr int NP = reduce_pairs<F>::value;
+  const int C = Cd * NP;  // columns of the partial rows
   const int octs = C >> 3;
   const int streams = blockDim.x / octs;
   const int oct = threadIdx.x % octs;
   const int rs = threadIdx.x / octs;
   const int c0 = oct * 8;
+  const int cd0 = NP == 1 ? c0 : c0 % Cd;  // column of the data rows
   const int64_t rows_per_chunk = (M + gridDim.y - 1) / gridDim.y;
   const int64_t r0 = blockIdx.y * rows_per_chunk;
   const int64_t r1 = min(M, r0 + rows_per_chunk);
@@ -483,17 +658,17 @@ __global__ void reduce8_part_kernel(const F f, float* p1, float* p2,
     typename F::Row v[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
-      f.load(v[u], (r + u * (int64_t)streams) * C + c0);
+      f.load(v[u], (r + u * (int64_t)streams) * Cd + cd0);
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) f.add(ch, v[u], a1, a2);
   }
   for (; r < r1; r += streams) {
     typename F::Row v;
-    f.load(v, r * C + c0);
+    f.load(v, r * Cd + cd0);
     f.add(ch, v, a1, a2);
   }
-  __shared__ float sh1[256][8];
-  __shared__ float sh2[F::kTwo ? 256 : 1][F::kTwo ? 8 : 1];
+  __shared__ float sh1[256 * NP][8];
+  __shared__ float sh2[F::kTwo ? 256 * NP : 1][F::kTwo ? 8 : 1];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     sh1[threadIdx.x][e] = a1[e];
@@ -523,8 +698,8 @@ __global__ void reduce8_part_kernel(const F f, float* p1, float* p2,
   // object
   static_assert(sizeof(sh1) >= kTicketLdsWide * sizeof(float), "tail LDS");
   if (tk.cnt)
-    ticket_finish<F::kTwo, F::kTailRows, true>(tk, p1, p2, 0, C, C,
-                                               &sh1[0][0]);
+    ticket_finish<F::kTwo, F::kTailRows, true, 256 * NP>(tk, p1, p2, 0, C,
+                                                         C, &sh1[0][0]);
 }
 
 // ------------------------------ apply kernels -------------------------------
@@ -653,6 +828,133 @@ __global__ void bn_act_bwd_apply8_kernel(
     }
     if (HAS_SKIP) st8(&dskip[r * C + c0], osk);
     st8(&dx[r * C + c0], o);
+  }
+}
+
+// ---- dual apply kernels: the element-wise code of the two kernels they
+// replace, back to back, with the tensor between them kept in a register
+
+template <typename T>
+__global__ void bn_act_fwd_dual_kernel(const T* __restrict__ x,
+                                       const T* __restrict__ xs,
+                                       const BnParams p, const BnParams ps,
+                                       T* __restrict__ y, int64_t n, int C,
+                                       int act) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const int c = i % C;
+    const float sk = bn_skip_elem<T>(ldf(&xs[i]), ps.mean[c], ps.rstd[c],
+                                     ps.gamma[c], ps.beta[c]);
+    const float xh = (ldf(&x[i]) - p.mean[c]) * p.rstd[c];
+    float pre = xh * p.gamma[c] + p.beta[c];
+    pre += sk;
+    stf(&y[i], apply_act(pre, act));
+  }
+}
+
+__global__ void bn_act_fwd_dual8_kernel(const bf16* __restrict__ x,
+                                        const bf16* __restrict__ xs,
+                                        const BnParams p, const BnParams ps,
+                                        bf16* __restrict__ y, int64_t M,
+                                        int C, int act) {
+  const int octs = C >> 3;
+  const int streams = (int)(((int64_t)blockDim.x * gridDim.y) / octs);
+  const int64_t gtid = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
+  const int oct = (int)(gtid % octs);
+  const int64_t rs = gtid / octs;
+  const int c0 = oct * 8;
+  const BnFold f = fold_oct(p, c0);
+  const BnFold fs = fold_oct(ps, c0);
+  for (int64_t r = rs; r < M; r += streams) {
+    bf16 v[8], vs[8], o[8];
+    ld8(v, &x[r * C + c0]);
+    ld8(vs, &xs[r * C + c0]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float sk = bn_skip_oct(b2f(vs[e]), fs.sc[e], fs.sh[e]);
+      float pre = b2f(v[e]) * f.sc[e] + f.sh[e];
+      pre += sk;
+      o[e] = f2b(apply_act(pre, act));
+    }
+    st8(&y[r * C + c0], o);
+  }
+}
+
+// s1/s2: [2C] sums, the skip BN's in the second half
+template <typename T>
+__global__ void bn_act_bwd_dual_apply_kernel(
+    const T* __restrict__ dy, const T* __restrict__ x,
+    const T* __restrict__ xs, const BnParams p, const BnParams ps,
+    const float* __restrict__ s1, const float* __restrict__ s2,
+    T* __restrict__ dx, T* __restrict__ dxs, int64_t n, int C, float Mf,
+    int act) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    const int c = i % C;
+    const float mu = p.mean[c], rs = p.rstd[c], gm = p.gamma[c];
+    const float mus = ps.mean[c], rss = ps.rstd[c], gms = ps.gamma[c];
+    const float xsv = ldf(&xs[i]);
+    const float sk = bn_skip_elem<T>(xsv, mus, rss, gms, ps.beta[c]);
+    const float dyv = ldf(&dy[i]);
+    const BnGrad g = bn_grad<true>(ldf(&x[i]), mu, rs, gm, p.beta[c], sk,
+                                   dyv, act);
+    stf(&dx[i], gm * rs * (g.dpre - s1[c] / Mf - g.xh * s2[c] / Mf));
+    const BnGrad gs = bn_grad<false>(xsv, mus, rss, gms, ps.beta[c], 0.f,
+                                     round_as<T>(g.dpre), ACT_LINEAR);
+    stf(&dxs[i],
+        gms * rss * (gs.dpre - s1[C + c] / Mf - gs.xh * s2[C + c] / Mf));
+  }
+}
+
+__global__ __launch_bounds__(256) void bn_act_bwd_dual_apply8_kernel(
+    const bf16* __restrict__ dy, const bf16* __restrict__ x,
+    const bf16* __restrict__ xs, const BnParams p, const BnParams ps,
+    const float* __restrict__ s1, const float* __restrict__ s2,
+    bf16* __restrict__ dx, bf16* __restrict__ dxs, int64_t M, int C,
+    float Mf, int act) {
+  const int octs = C >> 3;
+  const int streams = (int)(((int64_t)blockDim.x * gridDim.y) / octs);
+  const int64_t gtid = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
+  const int oct = (int)(gtid % octs);
+  const int64_t rs = gtid / octs;
+  const int c0 = oct * 8;
+  const float invM = 1.f / Mf;
+  const BnOct ch = load_oct(p, c0);
+  const BnOct cs = load_oct(ps, c0);
+  const BnFold fs = fold_oct(ps, c0);
+  float t1[8], t2[8], u1[8], u2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    t1[e] = s1[c0 + e] * invM;
+    t2[e] = s2[c0 + e] * invM;
+    u1[e] = s1[C + c0 + e] * invM;
+    u2[e] = s2[C + c0 + e] * invM;
+  }
+  for (int64_t r = rs; r < M; r += streams) {
+    bf16 vx[8], vdy[8], vxs[8], o[8], os[8];
+    ld8(vx, &x[r * C + c0]);
+    ld8(vdy, &dy[r * C + c0]);
+    ld8(vxs, &xs[r * C + c0]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xsv = b2f(vxs[e]);
+      const float sk = bn_skip_oct(xsv, fs.sc[e], fs.sh[e]);
+      const float dyv = b2f(vdy[e]);
+      const BnGrad g = bn_grad<true>(b2f(vx[e]), ch.mu[e], ch.rsd[e],
+                                     ch.gm[e], ch.bt[e], sk, dyv, act);
+      const float d1 =
+          __builtin_fmaf(dyv, act_grad_by_sign(g.pre, act), -t1[e]);
+      o[e] = f2b(ch.gm[e] * ch.rsd[e] * __builtin_fmaf(-g.xh, t2[e], d1));
+      const BnGrad gs = bn_grad<false>(xsv, cs.mu[e], cs.rsd[e], cs.gm[e],
+                                       cs.bt[e], 0.f, b2f(f2b(g.dpre)),
+                                       ACT_LINEAR);
+      os[e] = f2b(cs.gm[e] * cs.rsd[e] *
+                  __builtin_fmaf(-gs.xh, u2[e], gs.dpre - u1[e]));
+    }
+    st8(&dx[r * C + c0], o);
+    st8(&dxs[r * C + c0], os);
   }
 }
 
@@ -896,7 +1198,8 @@ template <typename F>
 static void launch_reduce(const F& f, float* p1, float* p2, int chunks,
                           int64_t M, int C, hipStream_t s,
                           const BnTicket& tk) {
-  hipLaunchKernelGGL((reduce_part_kernel<F>), dim3(cdiv(C, 64), chunks),
+  constexpr int NP = reduce_pairs<F>::value;
+  hipLaunchKernelGGL((reduce_part_kernel<F>), dim3(cdiv(NP * C, 64), chunks),
       dim3(256), 0, s, f, p1, p2, M, C, tk);
 }
 
@@ -904,8 +1207,9 @@ template <int UNROLL, typename F>
 static void launch_reduce8(const F& f, float* p1, float* p2, int chunks,
                            int64_t M, int C, hipStream_t s,
                            const BnTicket& tk) {
+  constexpr int NP = reduce_pairs<F>::value;
   hipLaunchKernelGGL((reduce8_part_kernel<UNROLL, F>), dim3(1, chunks),
-      dim3(256), 0, s, f, p1, p2, M, C, tk);
+      dim3(256 * NP), 0, s, f, p1, p2, M, C, tk);
 }
 
 // grid of the octet apply kernels: (1, nb) blocks of 256
@@ -970,28 +1274,47 @@ std::vector<torch::Tensor> bn_stats(torch::Tensor x,
 }
 
 // finalize mean/rstd from the conv-epilogue-fused column partials
-// (conv_fwd_stats): p1/p2 are [chunks, C] sum / sumsq rows, reduced in
-// fixed order. M = number of pixels (B*Ho*Wo).
+// (conv_fwd_stats): p1/p2 are [rows, C] sum / sumsq rows, reduced in fixed
+// order. M = number of pixels (B*Ho*Wo). The partials are reduced like any
+// other [rows][C] matrix: one launch of the scalar reduce skeleton over
+// chunks of 32 rows that finishes itself through the ticket tail and writes
+// mean, rstd and the running statistics there (make_finalize); without a
+// ticket page (first call inside a capture) the staged launches follow.
 std::vector<torch::Tensor> bn_stats_from_parts(
     torch::Tensor p1, torch::Tensor p2,
     c10::optional<torch::Tensor> running_mean,
     c10::optional<torch::Tensor> running_var,
     double momentum, double eps, int64_t M) {
-  TORCH_CHECK(p1.dim() == 2 && p1.sizes() == p2.sizes(),
+  TORCH_CHECK(p1.dim() == 2 && p1.sizes() == p2.sizes() &&
+              p1.scalar_type() == at::kFloat &&
+              p2.scalar_type() == at::kFloat,
               "bn_stats_from_parts: bad partials");
-  const int chunks = p1.size(0);
-  const int C = p1.size(1);
-  auto opt = p1.options();
+  auto a = p1.contiguous();
+  auto b = p2.contiguous();
+  const int64_t rows = a.size(0);
+  const int C = a.size(1);
+  auto opt = a.options();
   auto sum = torch::empty({C}, opt);
   auto sumsq = torch::empty({C}, opt);
   auto mean = torch::empty({C}, opt);
   auto rstd = torch::empty({C}, opt);
   auto s = at::cuda::getCurrentCUDAStream();
-  run_reduce_partials(p1.data_ptr<float>(), p2.data_ptr<float>(),
-                      sum.data_ptr<float>(), sumsq.data_ptr<float>(),
-                      chunks, C, opt, s,
-                      make_finalize(mean, rstd, running_mean, running_var,
-                                    M, momentum, eps));
+  const BnFinalize fin = make_finalize(mean, rstd, running_mean, running_var,
+                                       M, momentum, eps);
+  // 8 rows per thread: short enough to stay latency-light, long enough that
+  // the flagship's 8192-row layers finish in 256 chunk rows
+  const int chunks = (int)std::min<int64_t>(1024, cdiv(rows, (int64_t)32));
+  auto q1 = torch::empty({chunks, C}, opt);
+  auto q2 = torch::empty({chunks, C}, opt);
+  const BnFinish done(a, (int)cdiv(C, 64), chunks, C, sum.data_ptr<float>(),
+                      sumsq.data_ptr<float>(), opt, s, fin);
+  launch_reduce(PartsElem{a.data_ptr<float>(), b.data_ptr<float>()},
+                q1.data_ptr<float>(), q2.data_ptr<float>(), chunks, rows, C,
+                s, done.tk);
+  if (!done.tk.cnt)
+    run_reduce_partials(q1.data_ptr<float>(), q2.data_ptr<float>(),
+                        sum.data_ptr<float>(), sumsq.data_ptr<float>(),
+                        chunks, C, opt, s, fin);
   HIP_CHECK_LAST();
   return {mean, rstd};
 }
@@ -1109,6 +1432,126 @@ std::vector<torch::Tensor> bn_act_bwd(torch::Tensor dy, torch::Tensor x,
   // dgamma = s2, dbeta = s1; dskip (= dpre) last when skip given
   if (has_skip) return {dx, s2, s1, dsk};
   return {dx, s2, s1};
+}
+
+// ---- dual forms: main BN on x, skip BN (Linear) on xs; see the file header
+
+static void check_dual(const torch::Tensor& xc, const torch::Tensor& xsc) {
+  TORCH_CHECK(xc.sizes() == xsc.sizes() &&
+              xc.scalar_type() == xsc.scalar_type(),
+              "bn dual: x and xs must agree in shape and dtype");
+}
+
+torch::Tensor bn_act_fwd_dual(torch::Tensor x, torch::Tensor mean,
+                              torch::Tensor rstd, torch::Tensor gamma,
+                              torch::Tensor beta, torch::Tensor xs,
+                              torch::Tensor mean_s, torch::Tensor rstd_s,
+                              torch::Tensor gamma_s, torch::Tensor beta_s,
+                              int64_t act) {
+  auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
+  auto xsc = xs.contiguous(at::MemoryFormat::ChannelsLast);
+  check_dual(xc, xsc);
+  const int C = xc.size(1);
+  const int64_t n = xc.numel();
+  const int64_t M = n / C;
+  auto y = torch::empty_like(xc);
+  auto gm = gamma.to(at::kFloat).contiguous();
+  auto bt = beta.to(at::kFloat).contiguous();
+  auto gms = gamma_s.to(at::kFloat).contiguous();
+  auto bts = beta_s.to(at::kFloat).contiguous();
+  auto s = at::cuda::getCurrentCUDAStream();
+  const BnParams p = bn_params(mean, rstd, gm, bt);
+  const BnParams ps = bn_params(mean_s, rstd_s, gms, bts);
+  if (fast8_ok(xc, C)) {
+    hipLaunchKernelGGL(bn_act_fwd_dual8_kernel, dim3(1, rows8_blocks(M, C)),
+        dim3(256), 0, s, ptr<const bf16>(xc), ptr<const bf16>(xsc), p, ps,
+        ptr<bf16>(y), M, C, (int)act);
+  } else {
+    with_dtype(xc, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((bn_act_fwd_dual_kernel<T>), dim3(ew_grid(n, 256)),
+          dim3(256), 0, s, ptr<const T>(xc), ptr<const T>(xsc), p, ps,
+          ptr<T>(y), n, C, (int)act);
+    });
+  }
+  HIP_CHECK_LAST();
+  return y;
+}
+
+// {dx, dgamma, dbeta, dxs, dgamma_s, dbeta_s}
+std::vector<torch::Tensor> bn_act_bwd_dual(
+    torch::Tensor dy, torch::Tensor x, torch::Tensor mean,
+    torch::Tensor rstd, torch::Tensor gamma, torch::Tensor beta,
+    torch::Tensor xs, torch::Tensor mean_s, torch::Tensor rstd_s,
+    torch::Tensor gamma_s, torch::Tensor beta_s, int64_t act) {
+  auto xc = x.contiguous(at::MemoryFormat::ChannelsLast);
+  auto xsc = xs.contiguous(at::MemoryFormat::ChannelsLast);
+  check_dual(xc, xsc);
+  auto dyc = dy.to(xc.scalar_type()).contiguous(at::MemoryFormat::ChannelsLast);
+  const int C = xc.size(1);
+  const int64_t n = xc.numel();
+  const int64_t M = n / C;
+  const auto fopt = xc.options().dtype(at::kFloat);
+  // [2C]: the main BN's sums, then the skip BN's
+  auto s1 = torch::empty({2 * C}, fopt);
+  auto s2 = torch::empty({2 * C}, fopt);
+  auto dx = torch::empty_like(xc);
+  auto dxs = torch::empty_like(xc);
+  auto gm = gamma.to(at::kFloat).contiguous();
+  auto bt = beta.to(at::kFloat).contiguous();
+  auto gms = gamma_s.to(at::kFloat).contiguous();
+  auto bts = beta_s.to(at::kFloat).contiguous();
+  auto s = at::cuda::getCurrentCUDAStream();
+  const BnParams p = bn_params(mean, rstd, gm, bt);
+  const BnParams ps = bn_params(mean_s, rstd_s, gms, bts);
+
+  // the chunking of the separate kernels: M and C, not 2C
+  const int chunks = pick_chunks(M, C);
+  auto p1 = torch::empty({chunks, 2 * C}, fopt);
+  auto p2 = torch::empty({chunks, 2 * C}, fopt);
+  float* p1p = p1.data_ptr<float>();
+  float* p2p = p2.data_ptr<float>();
+  float* s1p = s1.data_ptr<float>();
+  float* s2p = s2.data_ptr<float>();
+  const bool fast8 = fast8_ok(xc, C);
+  const BnFinish done(xc, fast8 ? 1 : (int)cdiv(2 * C, 64), chunks, 2 * C,
+                      s1p, s2p, fopt, s);
+  auto run = [&](auto tag, auto octet) {
+    using T = typename decltype(tag)::type;
+    constexpr bool OCT = decltype(octet)::value;
+    const T* pdy = ptr<const T>(dyc);
+    const T* px = ptr<const T>(xc);
+    const T* pxs = ptr<const T>(xsc);
+    if constexpr (OCT) {
+      // not unrolled: two rows of three loads in flight put the functor's
+      // 64 hoisted parameters over the 128 registers of a 512-thread block
+      // (the adds keep their order whatever the unroll)
+      launch_reduce8<1>(BnBwdDualRow8{pdy, px, pxs, p, ps, (int)act, C}, p1p,
+                        p2p, chunks, M, C, s, done.tk);
+    } else {
+      launch_reduce(BnBwdDualElem<T>{pdy, px, pxs, p, ps, (int)act, C}, p1p,
+                    p2p, chunks, M, C, s, done.tk);
+    }
+    if (!done.tk.cnt)
+      run_reduce_partials(p1p, p2p, s1p, s2p, chunks, 2 * C, fopt, s);
+    if constexpr (OCT) {
+      hipLaunchKernelGGL(bn_act_bwd_dual_apply8_kernel,
+          dim3(1, rows8_blocks(M, C)), dim3(256), 0, s, pdy, px, pxs, p, ps,
+          s1p, s2p, ptr<T>(dx), ptr<T>(dxs), M, C, (float)M, (int)act);
+    } else {
+      hipLaunchKernelGGL((bn_act_bwd_dual_apply_kernel<T>),
+          dim3(ew_grid(n, 256)), dim3(256), 0, s, pdy, px, pxs, p, ps, s1p,
+          s2p, ptr<T>(dx), ptr<T>(dxs), n, C, (float)M, (int)act);
+    }
+  };
+  if (fast8) {
+    run(TypeTag<bf16>{}, std::true_type{});
+  } else {
+    with_dtype(xc, [&](auto tag) { run(tag, std::false_type{}); });
+  }
+  HIP_CHECK_LAST();
+  return {dx, s2.narrow(0, 0, C), s1.narrow(0, 0, C), dxs,
+          s2.narrow(0, C, C), s1.narrow(0, C, C)};
 }
 
 // plain column sum (conv dbias): sum over rows of (M, C)

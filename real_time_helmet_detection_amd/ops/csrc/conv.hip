@@ -493,8 +493,9 @@ namespace {
 
 // variants: 0 = the 128x128/K32 kernel of this file, 1 = 64x64 split-K
 // (small spatial / Cout<=64 fill), 2 = 128x128/K64 double-buffer (fewer
-// barriers+glds issues per channel), 3 = halo-tile 3x3 (conv_halo.hip; it
-// has no stats epilogue: conv_fwd_stats then runs `alt`, the faster of 0/2)
+// barriers+glds issues per channel), 3 = halo-tile 3x3 (conv_halo.hip; its
+// stats epilogue needs Cout % 8 == 0: conv_fwd_stats otherwise runs `alt`,
+// the faster of 0/2)
 struct ConvChoice { int small; int splitk; int alt = 0; };
 
 std::mutex g_conv_tune_mu;
@@ -633,16 +634,23 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wpk,
 
 // ---------------------- training-BN fused-stats forward ---------------------
 // y = act(conv*scale + shift) PLUS the per-column sum/sumsq partials the
-// BN stats need — saves the standalone colsum pass over y (0.4 ms/step in
-// the round-2 profile). Returns {y, p1, p2}; p1/p2 are [2*Mblks, Cout]
-// fp32 partial rows reduced by bn_stats_from_parts in fixed order
-// (deterministic). When the autotuned variant for this shape is the
-// split-K small kernel (no stats epilogue), returns {y} and the caller
-// falls back to the standalone reduction.
+// BN stats need — saves the standalone colsum pass over y. Returns
+// {y, p1, p2}; p1/p2 are fp32 [rows, Cout] partial rows that
+// bn_stats_from_parts reduces in fixed order (deterministic): one row per
+// 8x16 tile from the halo kernel, 2*Mblks rows from the 128-tile kernels.
+// Returns {y} where the shape's variant has no stats epilogue (split-K) or
+// the caller's rule declines it; the caller then runs bn_stats.
+//
+// halo_min_tiles < 0: every variant with a stats epilogue uses it (the
+// RTHD_FUSED_STATS=1 meaning). halo_min_tiles >= 0: only the halo kernel
+// does, and only on shapes of at least that many tiles — the 128-tile
+// kernels' stats epilogue is a measured loss, and below the threshold the
+// colsum pass is launch-bound and the finish launch costs as much
+// (profiles/bn_passes.md). Any other shape runs its plain variant.
 std::vector<torch::Tensor> conv_fwd_stats(
     torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
     torch::Tensor shift, int64_t KH, int64_t KW, int64_t stride,
-    int64_t pad, int64_t Cout, int64_t act) {
+    int64_t pad, int64_t Cout, int64_t act, int64_t halo_min_tiles) {
   TORCH_CHECK(wpk.scalar_type() == at::kBFloat16,
               "conv_fwd_stats: bf16 only (f32 path uses bn_stats)");
   const ConvGeo g = make_conv_geo("conv_fwd_stats", x, wpk, KH, KW, stride,
@@ -650,16 +658,31 @@ std::vector<torch::Tensor> conv_fwd_stats(
   auto o = prep_conv_operands(g, x, wpk, scale, shift, c10::nullopt,
                               at::kBFloat16, at::kBFloat16);
   const ConvChoice ch = choose_conv_variant(g, o, (int)act);
+  const auto fopt = o.x.options().dtype(at::kFloat);
+  if (ch.small == 3 && halo_stats_ok(g) &&
+      halo_stats_rows(g) >= halo_min_tiles) {
+    auto p1 = torch::empty({halo_stats_rows(g), Cout}, fopt);
+    auto p2 = torch::empty_like(p1);
+    launch_halo_stats(g, o, (int)act, p1.data_ptr<float>(),
+                      p2.data_ptr<float>(), (int)Cout);
+    return {o.y, p1, p2};
+  }
+  if (halo_min_tiles >= 0) {
+    if (ch.small == 1)      launch_small(g, o, (int)act, ch.splitk);
+    else if (ch.small == 2) launch_k64(g, o, (int)act, nullptr, nullptr);
+    else if (ch.small == 3) launch_halo(g, o, (int)act);
+    else                    launch_big(g, o, (int)act, nullptr, nullptr);
+    return {o.y};
+  }
   if (ch.small == 1) {
     // split-K variant has no stats epilogue — caller runs bn_stats
     launch_small(g, o, (int)act, ch.splitk);
     return {o.y};
   }
-  auto p1 = torch::empty({2 * cdiv(g.M, 128), Cout},
-                         o.x.options().dtype(at::kFloat));
+  auto p1 = torch::empty({2 * cdiv(g.M, 128), Cout}, fopt);
   auto p2 = torch::empty_like(p1);
-  // the halo variant has no stats epilogue: its shapes keep the faster of
-  // the two 128-tile kernels here
+  // a halo shape whose Cout has no wide epilogue keeps the faster of the
+  // two 128-tile kernels here
   const int variant = ch.small == 3 ? ch.alt : ch.small;
   if (variant == 2)
     launch_k64(g, o, (int)act, p1.data_ptr<float>(), p2.data_ptr<float>());
@@ -669,4 +692,3 @@ std::vector<torch::Tensor> conv_fwd_stats(
 }
 
 }  // namespace rthd
-

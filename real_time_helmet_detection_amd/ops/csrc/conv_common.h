@@ -324,9 +324,15 @@ void launch_k64(const ConvGeo& g, const ConvOperands& o, int act,
                 float* p1, float* p2);                      // conv_k64.hip
 void launch_small(const ConvGeo& g, const ConvOperands& o, int act,
                   int splitk);                              // conv_small.hip
-// halo-tile 3x3 variant: the shapes it takes, and its launcher (no stats)
+// halo-tile 3x3 variant: the shapes it takes, and its launcher
 bool halo_eligible(const ConvGeo& g);                       // conv_halo.hip
 void launch_halo(const ConvGeo& g, const ConvOperands& o, int act);
+// ... with the BN-stats epilogue (halo_stats_ok shapes, no skip): row t of
+// p1/p2[halo_stats_rows][ld] = sum / sumsq of tile t's rounded outputs
+bool halo_stats_ok(const ConvGeo& g);
+int64_t halo_stats_rows(const ConvGeo& g);
+void launch_halo_stats(const ConvGeo& g, const ConvOperands& o, int act,
+                       float* p1, float* p2, int ld);
 // halo-tile fp8 3x3 variant on prepared e4m3 operands  (conv_halo_fp8.hip)
 bool fp8_halo_eligible(const ConvGeo& g);
 void launch_halo_fp8(const ConvGeo& g, const ConvOperands& o, int act,
@@ -346,7 +352,12 @@ torch::Tensor conv_fwd(torch::Tensor x, torch::Tensor wpk,
 std::vector<torch::Tensor> conv_fwd_stats(
     torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
     torch::Tensor shift, int64_t KH, int64_t KW, int64_t stride,
-    int64_t pad, int64_t Cout, int64_t act);
+    int64_t pad, int64_t Cout, int64_t act, int64_t halo_min_tiles);
+std::vector<torch::Tensor> conv_fwd_halo_stats(
+    torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
+    torch::Tensor shift, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
+    int64_t Cout, int64_t act, c10::optional<torch::Tensor> p1,
+    c10::optional<torch::Tensor> p2);
 torch::Tensor conv_fwd_k64(torch::Tensor x, torch::Tensor wpk,
                            torch::Tensor scale, torch::Tensor shift,
                            c10::optional<torch::Tensor> skip,

@@ -36,10 +36,12 @@ namespace {
 
 // CIN: input channels (64 or 128, = the packed Cinp). MI: image rows per
 // wave; the tile is 2*MI rows x 16 px. WIDE (no skip): the bf16 tile goes
-// through LDS and leaves as 16-B stores.
+// through LDS and leaves as 16-B stores. STATS (WIDE only): the block also
+// writes its row of the BN column partials sp1/sp2[tile][ld]
+// (halo_epilogue_wide).
 // conv_halo_kernel reads its fragments with lds_read_b128 and waits of its
 // own: the audit rule of lds_async.h applies to every edit.
-template <int CIN, int MI, bool HAS_SKIP, bool WIDE>
+template <int CIN, int MI, bool HAS_SKIP, bool WIDE, bool STATS = false>
 __global__ __launch_bounds__(256)
 void conv_halo_kernel(const bf16* __restrict__ x,
                       const bf16* __restrict__ wpk,
@@ -47,8 +49,11 @@ void conv_halo_kernel(const bf16* __restrict__ x,
                       const float* __restrict__ shift,
                       const bf16* __restrict__ skip,
                       const bf16* __restrict__ zpage,
-                      bf16* __restrict__ y, HaloGeo g, int act) {
+                      bf16* __restrict__ y, HaloGeo g, int act,
+                      float* __restrict__ sp1, float* __restrict__ sp2,
+                      int ld) {
   static_assert(!(HAS_SKIP && WIDE), "the wide epilogue has no skip input");
+  static_assert(!STATS || WIDE, "stats ride on the wide epilogue");
   constexpr int TH = 2 * MI;
   using G = HaloBf16<CIN>;
   constexpr int KC = CIN / 32;
@@ -158,8 +163,8 @@ void conv_halo_kernel(const bf16* __restrict__ x,
   float esc[4], esh[4];
   halo_load_scale_shift(scale, shift, col0, g.Cout, esc, esh);
   if (WIDE)
-    halo_epilogue_wide<MI>(acc, esc, esh, y, g, smem, nblk, b, ty0, tx0, tid,
-                           wr, wc, act);
+    halo_epilogue_wide<MI, STATS>(acc, esc, esh, y, g, smem, nblk, b, ty0,
+                                  tx0, tid, wr, wc, act, sp1, sp2, ld);
   else
     halo_epilogue_scalar<HAS_SKIP, MI>(acc, esc, esh, skip, y, g, b, ty0, tx0,
                                        wr, lane, col0, act);
@@ -173,25 +178,47 @@ void conv_halo_kernel(const bf16* __restrict__ x,
 constexpr int HALO_MI = 4;
 constexpr int HALO_TH = 2 * HALO_MI;
 
-template <int CIN, int MI, bool HAS_SKIP, bool WIDE>
-void halo_launch_inst(const HaloGeo& hg, const ConvOperands& o, int act) {
+// sp: the stats instantiation's partial rows (sp.p1 == nullptr: none)
+struct HaloStatsOut {
+  float* p1 = nullptr;
+  float* p2 = nullptr;
+  int ld = 0;
+};
+
+template <int CIN, int MI, bool HAS_SKIP, bool WIDE, bool STATS = false>
+void halo_launch_inst(const HaloGeo& hg, const ConvOperands& o, int act,
+                      const HaloStatsOut& sp = HaloStatsOut{}) {
   static_assert(!WIDE || halo_lds_bytes<HaloBf16<CIN>>(2 * MI) >=
                              2 * MI * 16 * 256,
                 "the output tile must fit in the LDS of the main loop");
-  halo_launch<&conv_halo_kernel<CIN, MI, HAS_SKIP, WIDE>, HaloBf16<CIN>, MI,
-              bf16, bf16>("conv_halo", hg, o, act);
+  halo_launch<&conv_halo_kernel<CIN, MI, HAS_SKIP, WIDE, STATS>,
+              HaloBf16<CIN>, MI, bf16, bf16>("conv_halo", hg, o, act, sp.p1,
+                                             sp.p2, sp.ld);
 }
 
 // The wide epilogue needs whole 16-B chunks of output channels and has no
-// skip input; the other calls take the scalar one.
+// skip input; the other calls take the scalar one. Stats ride on the wide
+// epilogue only (halo_stats_ok).
 template <int CIN>
-void halo_launch_cin(const HaloGeo& hg, const ConvOperands& o, int act) {
-  if (o.skip.defined())
+void halo_launch_cin(const HaloGeo& hg, const ConvOperands& o, int act,
+                     const HaloStatsOut& sp) {
+  if (sp.p1)
+    halo_launch_inst<CIN, HALO_MI, false, true, true>(hg, o, act, sp);
+  else if (o.skip.defined())
     halo_launch_inst<CIN, HALO_MI, true, false>(hg, o, act);
   else if (hg.Cout % 8 == 0)
     halo_launch_inst<CIN, HALO_MI, false, true>(hg, o, act);
   else
     halo_launch_inst<CIN, HALO_MI, false, false>(hg, o, act);
+}
+
+void launch_halo_impl(const ConvGeo& g, const ConvOperands& o, int act,
+                      const HaloStatsOut& sp) {
+  halo_check_eligible("conv_halo", g, halo_eligible(g), "64 or 128", HALO_TH);
+  const HaloGeo hg = make_halo_geo(g, HALO_TH);
+  if (g.Cin == 128) halo_launch_cin<128>(hg, o, act, sp);
+  else              halo_launch_cin<64>(hg, o, act, sp);
+  HIP_CHECK_LAST();
 }
 
 }  // namespace
@@ -201,11 +228,25 @@ bool halo_eligible(const ConvGeo& g) {
 }
 
 void launch_halo(const ConvGeo& g, const ConvOperands& o, int act) {
-  halo_check_eligible("conv_halo", g, halo_eligible(g), "64 or 128", HALO_TH);
-  const HaloGeo hg = make_halo_geo(g, HALO_TH);
-  if (g.Cin == 128) halo_launch_cin<128>(hg, o, act);
-  else              halo_launch_cin<64>(hg, o, act);
-  HIP_CHECK_LAST();
+  launch_halo_impl(g, o, act, HaloStatsOut{});
+}
+
+bool halo_stats_ok(const ConvGeo& g) {
+  return halo_eligible(g) && g.Cout % 8 == 0;
+}
+
+int64_t halo_stats_rows(const ConvGeo& g) {
+  return (int64_t)g.B * (g.H / HALO_TH) * (g.W / HALO_TW);
+}
+
+void launch_halo_stats(const ConvGeo& g, const ConvOperands& o, int act,
+                       float* p1, float* p2, int ld) {
+  TORCH_CHECK(halo_stats_ok(g) && !o.skip.defined(),
+              "conv_halo stats: needs an eligible shape, Cout % 8 == 0 and "
+              "no skip");
+  TORCH_CHECK(p1 && p2 && ld >= g.Cout && ld % 4 == 0,
+              "conv_halo stats: bad partial rows");
+  launch_halo_impl(g, o, act, HaloStatsOut{p1, p2, ld});
 }
 
 torch::Tensor conv_fwd_halo(torch::Tensor x, torch::Tensor wpk,
@@ -221,6 +262,45 @@ torch::Tensor conv_fwd_halo(torch::Tensor x, torch::Tensor wpk,
                               at::kBFloat16);
   launch_halo(g, o, (int)act);
   return o.y;
+}
+
+// The halo variant with its stats epilogue, forced (tests, kbench). p1/p2:
+// optional caller-owned fp32 [rows >= tiles][cols >= Cout] partial buffers
+// (unit column stride, 16-B aligned rows); rows [0, tiles) x columns
+// [0, Cout) are written and nothing else. Returns {y, p1, p2}.
+std::vector<torch::Tensor> conv_fwd_halo_stats(
+    torch::Tensor x, torch::Tensor wpk, torch::Tensor scale,
+    torch::Tensor shift, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
+    int64_t Cout, int64_t act, c10::optional<torch::Tensor> p1,
+    c10::optional<torch::Tensor> p2) {
+  TORCH_CHECK(wpk.scalar_type() == at::kBFloat16,
+              "conv_fwd_halo_stats: bf16 packed weights required");
+  TORCH_CHECK(p1.has_value() == p2.has_value(),
+              "conv_fwd_halo_stats: p1 and p2 go together");
+  const ConvGeo g = make_conv_geo("conv_fwd_halo_stats", x, wpk, KH, KW,
+                                  stride, pad, Cout, 64);
+  auto o = prep_conv_operands(g, x, wpk, scale, shift, c10::nullopt,
+                              at::kBFloat16, at::kBFloat16);
+  TORCH_CHECK(halo_stats_ok(g), "conv_fwd_halo_stats: shape not eligible");
+  const int64_t rows = halo_stats_rows(g);
+  torch::Tensor a, b;
+  if (p1.has_value()) {
+    a = *p1;
+    b = *p2;
+    for (const torch::Tensor* t : {&a, &b})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat &&
+                  t->dim() == 2 && t->size(0) >= rows && t->size(1) >= Cout &&
+                  t->stride(1) == 1 && t->stride(0) == a.stride(0) &&
+                  t->stride(0) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "conv_fwd_halo_stats: bad partial buffer");
+  } else {
+    a = torch::empty({rows, Cout}, o.x.options().dtype(at::kFloat));
+    b = torch::empty_like(a);
+  }
+  launch_halo_stats(g, o, (int)act, a.data_ptr<float>(), b.data_ptr<float>(),
+                    (int)a.stride(0));
+  return {o.y, a, b};
 }
 
 }  // namespace rthd

@@ -99,14 +99,26 @@ DEV_INLINE void halo_epilogue_scalar(const f32x4 (&acc)[MI][4],
 // the writing lane group's pixel quad so the four groups of a store hit
 // different banks) and leaves as 16 B per lane. The tile must fit in the
 // LDS of the main loop (the caller's static_assert).
-template <int MI, typename OUT_T>
+//
+// STATS (bf16 out, TH = 8): the block also writes row `tile` of the BN
+// column partials sp1/sp2[tile][ld] = sum / sum of squares of the ROUNDED
+// outputs of its 128 pixels, channels nblk*128 .. < Cout. In the store loop
+// a thread keeps one channel octet (256 % CPR == 0) and adds its 8 pixels
+// from the registers it stores from; the 16 pixel groups of a channel are
+// then summed through the tile's LDS in group order by wave 0 and leave as
+// 16-B stores. Every partial row has one owner: no atomics, no memset,
+// fixed order.
+template <int MI, bool STATS = false, typename OUT_T>
 DEV_INLINE void halo_epilogue_wide(const f32x4 (&acc)[MI][4],
                                    const float (&esc)[4],
                                    const float (&esh)[4],
                                    OUT_T* __restrict__ y, const HaloGeo& g,
                                    char* smem,
                                    int nblk, int b, int ty0, int tx0,
-                                   int tid, int wr, int wc, int act) {
+                                   int tid, int wr, int wc, int act,
+                                   float* __restrict__ sp1 = nullptr,
+                                   float* __restrict__ sp2 = nullptr,
+                                   int ld = 0) {
   const int lane = tid & 63;
   constexpr int TH = 2 * MI;
   constexpr int ES = (int)sizeof(OUT_T);
@@ -132,6 +144,60 @@ DEV_INLINE void halo_epilogue_wide(const f32x4 (&acc)[MI][4],
     }
   }
   __syncthreads();
+  if constexpr (STATS) {
+    static_assert(ES == 2 && 256 % CPR == 0, "bf16 tile, fixed octet");
+    constexpr int NG = 256 / CPR;  // pixel groups; thread = (group, octet)
+    const int ch = tid % CPR, pg = tid / CPR;
+    const int c = nblk * HALO_BN + ch * EPC;
+    float s[8] = {}, q[8] = {};
+    if (c < g.Cout) {
+#pragma unroll
+      for (int i = 0; i < TH * 16 / NG; ++i) {
+        const int pl = i * NG + pg;
+        const int chunk = ch ^ (((pl >> 2) & 3) << 1);
+        const i32x4 v =
+            *reinterpret_cast<const i32x4*>(smem + pl * ROWB + chunk * 16);
+        const int64_t m =
+            ((int64_t)b * g.H + ty0 + (pl >> 4)) * g.W + tx0 + (pl & 15);
+        *reinterpret_cast<i32x4*>(y + m * g.Cout + c) = v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t u = (uint32_t)v[k];
+          const float lo = __uint_as_float(u << 16);
+          const float hi = __uint_as_float(u & 0xffff0000u);
+          s[2 * k] += lo;
+          q[2 * k] += lo * lo;
+          s[2 * k + 1] += hi;
+          q[2 * k + 1] += hi * hi;
+        }
+      }
+    }
+    __syncthreads();  // every thread has read its part of the tile
+    // red[sum | sumsq][group][128 channels], 2 * NG * 512 B <= the tile
+    static_assert(2 * NG * HALO_BN * 4 <= TH * 16 * ROWB, "partials fit");
+    float* red = reinterpret_cast<float*>(smem);
+    f32x4* r1 = reinterpret_cast<f32x4*>(red + pg * HALO_BN + ch * EPC);
+    f32x4* r2 = reinterpret_cast<f32x4*>(red + (NG + pg) * HALO_BN + ch * EPC);
+    r1[0] = f32x4{s[0], s[1], s[2], s[3]};
+    r1[1] = f32x4{s[4], s[5], s[6], s[7]};
+    r2[0] = f32x4{q[0], q[1], q[2], q[3]};
+    r2[1] = f32x4{q[4], q[5], q[6], q[7]};
+    __syncthreads();
+    if (tid < 64) {
+      const int which = tid >> 5, c4 = (tid & 31) * 4;
+      const float* src = red + which * NG * HALO_BN + c4;
+      f32x4 a = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+      for (int k = 1; k < NG; ++k)
+        a += *reinterpret_cast<const f32x4*>(src + k * HALO_BN);
+      const int cg = nblk * HALO_BN + c4;
+      const int64_t tile = ((int64_t)b * g.tiles_y + ty0 / TH) * g.tiles_x +
+                           tx0 / HALO_TW;
+      if (cg < g.Cout)
+        *reinterpret_cast<f32x4*>((which ? sp2 : sp1) + tile * ld + cg) = a;
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < TH * 16 * CPR / 256; ++i) {
     const int idx = i * 256 + tid;
@@ -176,10 +242,12 @@ inline HaloGeo make_halo_geo(const ConvGeo& g, int TH) {
 
 // one block per (tile, n block); LDS = patch + weight ring, opted in to
 // where that is above 64 KB. The zero page is 16 zero bytes for any T.
-// KERN(const T* x, wpk, scale, shift, skip, zpage, OUT_T* y, HaloGeo, act)
-template <auto KERN, typename G, int MI, typename T, typename OUT_T>
+// KERN(const T* x, wpk, scale, shift, skip, zpage, OUT_T* y, HaloGeo, act,
+//      extra...)
+template <auto KERN, typename G, int MI, typename T, typename OUT_T,
+          typename... Extra>
 void halo_launch(const char* who, const HaloGeo& hg, const ConvOperands& o,
-                 int act) {
+                 int act, Extra... extra) {
   constexpr int lds = halo_lds_bytes<G>(2 * MI);
   lds_opt_in<KERN>(lds, who);
   const dim3 grid((unsigned)(hg.B * hg.tiles_y * hg.tiles_x *
@@ -189,7 +257,7 @@ void halo_launch(const char* who, const HaloGeo& hg, const ConvOperands& o,
       conv_ptr<const T>(o.wpk), o.scale.data_ptr<float>(),
       o.shift.data_ptr<float>(), conv_ptr<const T>(o.skip),
       reinterpret_cast<const T*>(zero_page_bf16(o.x)), conv_ptr<OUT_T>(o.y),
-      hg, act);
+      hg, act, extra...);
 }
 
 }  // namespace rthd

@@ -80,6 +80,19 @@ def conv_bn_act(x, conv, bn=None, act='Linear', act_module=None,
     return _named_act(y, act)
 
 
+def conv_bn_act_skipconv(x, conv, bn, act, training, sx, sconv, sbn):
+    """act(bn(conv(x)) + bn_s(sconv(sx))): the tail of a Residual whose skip
+    is itself conv+BN (Linear). On the HIP training path the skip BN is
+    applied inside the main BN's passes (hip.conv_bn_act_dual); everywhere
+    else this is the two conv_bn_act calls it stands for."""
+    if _hip(x):
+        from . import hip
+        if hip.dual_bn_applies(x, conv, bn, act, sx, sconv, sbn, training):
+            return hip.conv_bn_act_dual(x, conv, bn, act, sx, sconv, sbn)
+    s = conv_bn_act(sx, sconv, sbn, 'Linear', None, training)
+    return conv_bn_act(x, conv, bn, act, None, training, skip=s)
+
+
 def add_act(a, b, act='Linear', act_module=None):
     """Residual add followed by activation (fused elementwise on HIP)."""
     if _hip(a):

@@ -93,6 +93,13 @@ def _ones_zeros(n, device):
 
 # ------------------------------------------------------------------ conv ---
 
+# RTHD_FUSED_STATS=halo: smallest tile count (8x16-pixel tiles, batch
+# included) at which the halo conv's stats epilogue plus the one-launch
+# finish beats the standalone colsum pass; a fixed rule, so eager runs and
+# captured graphs agree (profiles/bn_passes.md).
+_HALO_STATS_MIN_TILES = 512
+
+
 def _stem_col_weight(weight):
     """(Cout,3,KS,KS) -> (Cout, KS*KS*3 padded to x8, 1, 1): column t*3+ci,
     matching stem_im2col's unfolded layout (7x7: 147 -> 152 cols)."""
@@ -104,12 +111,144 @@ def _stem_col_weight(weight):
     return w.reshape(cout, -1, 1, 1)
 
 
+def _conv_lin_stats(C, xc, wpk, ones, bias_f, kh, kw, stride, pad, cout,
+                    stem_col, bf16, rmean, rvar, momentum, eps):
+    """Training-BN front half: y_lin = conv(x) + bias and the batch
+    statistics of y_lin (running stats updated). Returns y_lin, mean, rstd.
+
+    BN statistics from the conv's own epilogue (conv_fwd_stats +
+    bn_stats_from_parts) save the colsum pass that re-reads y_lin, but they
+    group the fp32 sums differently from bn_stats, and a training run
+    amplifies that: after six steps the flagship's outputs differ from the
+    colsum path's by up to 0.4 (profiles/bn_passes.md §4). The default
+    therefore stays conv, then bn_stats; RTHD_FUSED_STATS opts in:
+      'halo': only where the halo-tile 3x3 kernel runs, on shapes of at
+              least _HALO_STATS_MIN_TILES tiles — its wide epilogue sums
+              from the registers it stores from (0.15 ms/step faster;
+              profiles/bn_passes.md has the per-shape table);
+      '1':    every kernel with a stats epilogue. In the 128-tile kernels
+              that measured ~6% SLOWER end to end than the colsum pass
+              (shuffles out of the MFMA layout and a longer store tail;
+              same-box A/B 940 vs 997 img/s);
+      unset or '0': never."""
+    lin = ACT_CODE['Linear']
+    if stem_col:
+        kh, kw, stride, pad = 1, 1, 1, 0
+    fused = os.environ.get('RTHD_FUSED_STATS')
+    if bf16 and fused in ('1', 'halo'):
+        min_tiles = -1 if fused == '1' else _HALO_STATS_MIN_TILES
+        outs = C.conv_fwd_stats(xc, wpk, ones, bias_f, kh, kw, stride, pad,
+                                cout, lin, min_tiles)
+        y_lin = outs[0]
+        if len(outs) == 3:
+            mean, rstd = C.bn_stats_from_parts(
+                outs[1], outs[2], rmean, rvar, momentum, eps,
+                y_lin.numel() // cout)
+            return y_lin, mean, rstd
+    else:
+        y_lin = _ops().conv_fwd(xc, wpk, ones, bias_f, None, kh, kw, stride,
+                                pad, cout, lin)
+    mean, rstd = C.bn_stats(y_lin, rmean, rvar, momentum, eps)
+    return y_lin, mean, rstd
+
+
+def _conv_input_weight_grads(C, xc, weight, dpre, kh, kw, stride, pad, bf16,
+                             is_stem, stem_col, wpk_t, need_dx, need_dw):
+    """dx (dgrad) and dw (wgrad, on the side stream) of a conv from the
+    gradient dpre of its linear output."""
+    # wgrad — on the side stream, overlapping the dgrad launched below
+    dw = None
+    if need_dw:
+        cur = torch.cuda.current_stream(xc.device)
+        side = _wgrad_stream(xc.device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            if stem_col:
+                # xc is the SAVED unfolded [px][152] tensor from the
+                # forward: the wgrad is its 1x1 MFMA case; column
+                # t*3+ci -> dW[co][ci][t]
+                cout = dpre.shape[1]
+                if xc.dtype == torch.bfloat16:
+                    dwc = C.wgrad_bf16_fast(xc, dpre, 1, 1, 1, 0)
+                else:
+                    dwc = C.wgrad(xc, dpre.float(), 1, 1, 1, 0)
+                dw = (dwc[:, :kh * kw * 3, 0, 0]
+                      .reshape(cout, kh * kw, 3).permute(0, 2, 1)
+                      .reshape(cout, 3, kh, kw).contiguous())
+            elif xc.dtype == torch.bfloat16:
+                # pad stray non-x8 channel counts (head Cout=6) so the
+                # aligned fast kernel runs; slice the result back
+                cin_p = xc.shape[1] % 8
+                cout_p = dpre.shape[1] % 8
+                xs = torch.nn.functional.pad(
+                    xc, (0, 0, 0, 0, 0, 8 - cin_p)).contiguous(
+                    memory_format=torch.channels_last) if cin_p else xc
+                ds = torch.nn.functional.pad(
+                    dpre, (0, 0, 0, 0, 0, 8 - cout_p)).contiguous(
+                    memory_format=torch.channels_last) if cout_p \
+                    else dpre
+                dw = C.wgrad_bf16_fast(xs, ds, kh, kw, stride, pad)
+                if cin_p or cout_p:
+                    dw = dw[:dpre.shape[1], :xc.shape[1]].contiguous(
+                        memory_format=torch.channels_last)
+            else:
+                dw = C.wgrad(xc, dpre, kh, kw, stride, pad)
+        cur.wait_stream(side)
+        dw.record_stream(cur)
+
+    # dgrad
+    dx = None
+    if need_dx:
+        if is_stem:
+            raise NotImplementedError(
+                'stem dgrad (3-channel input) is not needed: the image '
+                'is a leaf tensor')
+        cin = xc.shape[1]
+        ones, zeros = _ones_zeros(cin, xc.device)
+        if stride == 1:
+            bf16_d = bf16 and dpre.shape[1] % 8 == 0
+            if wpk_t is None:  # else packed by forward with wpk
+                wpk_t = C.pack_weights(weight, True, bf16_d)
+            dsrc = dpre if bf16_d else dpre.float()
+            dx = C.conv_fwd(dsrc, wpk_t, ones, zeros, None, kh, kw, 1,
+                            pad, cin, ACT_CODE['Linear'])
+            if dx.dtype != xc.dtype:
+                dx = dx.to(xc.dtype)
+        elif stride == 2 and kh == 2 and kw == 2 and pad == 0:
+            # k2/s2 windows don't overlap: each input pixel receives
+            # from exactly one output pixel, so dgrad decomposes into
+            # FOUR 1x1 convs (one per tap parity), scattered back into
+            # the interleaved input grid (the pool='Conv' downsampler).
+            dx = torch.empty_like(xc).contiguous(
+                memory_format=torch.channels_last)
+            for r in range(2):
+                for c in range(2):
+                    wt = weight[:, :, r:r + 1, c:c + 1]
+                    wpk_t = C.pack_weights(wt, True, bf16)
+                    part = C.conv_fwd(dpre, wpk_t, ones, zeros, None,
+                                      1, 1, 1, 0, cin,
+                                      ACT_CODE['Linear'])
+                    dx[:, :, r::2, c::2] = part
+        else:
+            raise NotImplementedError(
+                f'HIP dgrad for k={kh} stride={stride} not implemented')
+    return dx, dw
+
+
 class _ConvBNActFn(torch.autograd.Function):
+    """conv -> (BN) -> (+skip) -> act. With s_lin given (training BN only)
+    the skip is the BN, with batch statistics mean_s / rstd_s and affine
+    gamma_s / beta_s, of the linear conv output s_lin, applied in the same
+    pass (the dual kernels of bn.hip); backward then returns the gradient
+    of s_lin and of gamma_s / beta_s."""
+
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, rmean, rvar, skip,
                 kh, kw, stride, pad, act_code, use_bn, training, momentum,
-                eps, is_stem):
+                eps, is_stem, s_lin, mean_s, rstd_s, gamma_s, beta_s):
         C = _C()
+        dual = s_lin is not None
+        assert not dual or (use_bn and training and skip is None)
         # the bf16 glds staging needs 16-B channel chunks; rare non-multiple
         # channel counts (merge_prediction 6->128) take the exact-f32 path.
         # The stem has its own direct kernel (any Cin) and stays bf16.
@@ -160,31 +299,16 @@ class _ConvBNActFn(torch.autograd.Function):
         if use_bn and training:
             # conv output INCLUDES the (redundant-under-BN) bias so running
             # stats match the eager/reference semantics (stem has bias+BN).
-            # Fused-epilogue BN stats exist (conv_fwd_stats) but measured
-            # ~6% SLOWER end to end than the standalone colsum pass (the
-            # extra epilogue stores + shuffles extend the conv's
-            # store-tail more than the saved 0.4 ms read pass; same-box
-            # A/B 940 vs 997 img/s) — opt-in via RTHD_FUSED_STATS=1.
-            if bf16 and os.environ.get('RTHD_FUSED_STATS') == '1':
-                if stem_col:
-                    outs = C.conv_fwd_stats(xc, wpk, ones, bias_f, 1, 1,
-                                            1, 0, cout, ACT_CODE['Linear'])
-                else:
-                    outs = C.conv_fwd_stats(xc, wpk, ones, bias_f, kh, kw,
-                                            stride, pad, cout,
-                                            ACT_CODE['Linear'])
-                y_lin = outs[0]
-                if len(outs) == 3:
-                    mean, rstd = C.bn_stats_from_parts(
-                        outs[1], outs[2], rmean, rvar, momentum, eps,
-                        y_lin.numel() // cout)
-                else:
-                    mean, rstd = C.bn_stats(y_lin, rmean, rvar, momentum,
-                                            eps)
+            y_lin, mean, rstd = _conv_lin_stats(
+                C, xc, wpk, ones, bias_f, kh, kw, stride, pad, cout,
+                stem_col, bf16, rmean, rvar, momentum, eps)
+            if dual:
+                y = C.bn_act_fwd_dual(y_lin, mean, rstd, gamma, beta, s_lin,
+                                      mean_s, rstd_s, gamma_s, beta_s,
+                                      act_code)
             else:
-                y_lin = run_conv(ones, bias_f, ACT_CODE['Linear'])
-                mean, rstd = C.bn_stats(y_lin, rmean, rvar, momentum, eps)
-            y = C.bn_act_fwd(y_lin, mean, rstd, gamma, beta, act_code, skc)
+                y = C.bn_act_fwd(y_lin, mean, rstd, gamma, beta, act_code,
+                                 skc)
         elif use_bn:
             rstd_run = torch.rsqrt(rvar.float() + eps)
             scale = (gamma.float() * rstd_run).contiguous()
@@ -196,8 +320,12 @@ class _ConvBNActFn(torch.autograd.Function):
 
         ctx.meta = (kh, kw, stride, pad, act_code, use_bn, training, bf16,
                     is_stem, bias is not None, eps, skc is not None,
-                    stem_col)
-        if use_bn and training:
+                    stem_col, dual)
+        if dual:
+            ctx.save_for_backward(xc, weight, gamma, beta, y_lin, mean,
+                                  rstd, s_lin, mean_s, rstd_s, gamma_s,
+                                  beta_s)
+        elif use_bn and training:
             ctx.save_for_backward(xc, weight, gamma, beta, y_lin, mean,
                                   rstd, skc)
         elif use_bn:
@@ -213,10 +341,18 @@ class _ConvBNActFn(torch.autograd.Function):
     def backward(ctx, dy):
         C = _C()
         (kh, kw, stride, pad, act_code, use_bn, training, bf16, is_stem,
-         has_bias, eps, has_skip, stem_col) = ctx.meta
+         has_bias, eps, has_skip, stem_col, dual) = ctx.meta
         dgamma = dbeta = dbias = dskip = None
+        ds_lin = dgamma_s = dbeta_s = None
 
-        if use_bn and training:
+        if dual:
+            (xc, weight, gamma, beta, y_lin, mean, rstd, s_lin, mean_s,
+             rstd_s, gamma_s, beta_s) = ctx.saved_tensors
+            (dpre, dgamma, dbeta, ds_lin, dgamma_s,
+             dbeta_s) = C.bn_act_bwd_dual(dy, y_lin, mean, rstd, gamma, beta,
+                                          s_lin, mean_s, rstd_s, gamma_s,
+                                          beta_s, act_code)
+        elif use_bn and training:
             (xc, weight, gamma, beta, y_lin, mean, rstd,
              skc) = ctx.saved_tensors
             outs = C.bn_act_bwd(dy, y_lin, mean, rstd, gamma, beta,
@@ -250,85 +386,62 @@ class _ConvBNActFn(torch.autograd.Function):
             else:
                 dbias = C.col_sum(dpre)
 
-        # wgrad — on the side stream, overlapping the dgrad launched above
-        dw = None
-        if ctx.needs_input_grad[1]:
-            cur = torch.cuda.current_stream(xc.device)
-            side = _wgrad_stream(xc.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                if stem_col:
-                    # xc is the SAVED unfolded [px][152] tensor from the
-                    # forward: the wgrad is its 1x1 MFMA case; column
-                    # t*3+ci -> dW[co][ci][t]
-                    cout = dpre.shape[1]
-                    if xc.dtype == torch.bfloat16:
-                        dwc = C.wgrad_bf16_fast(xc, dpre, 1, 1, 1, 0)
-                    else:
-                        dwc = C.wgrad(xc, dpre.float(), 1, 1, 1, 0)
-                    dw = (dwc[:, :kh * kw * 3, 0, 0]
-                          .reshape(cout, kh * kw, 3).permute(0, 2, 1)
-                          .reshape(cout, 3, kh, kw).contiguous())
-                elif xc.dtype == torch.bfloat16:
-                    # pad stray non-x8 channel counts (head Cout=6) so the
-                    # aligned fast kernel runs; slice the result back
-                    cin_p = xc.shape[1] % 8
-                    cout_p = dpre.shape[1] % 8
-                    xs = torch.nn.functional.pad(
-                        xc, (0, 0, 0, 0, 0, 8 - cin_p)).contiguous(
-                        memory_format=torch.channels_last) if cin_p else xc
-                    ds = torch.nn.functional.pad(
-                        dpre, (0, 0, 0, 0, 0, 8 - cout_p)).contiguous(
-                        memory_format=torch.channels_last) if cout_p                         else dpre
-                    dw = C.wgrad_bf16_fast(xs, ds, kh, kw, stride, pad)
-                    if cin_p or cout_p:
-                        dw = dw[:dpre.shape[1], :xc.shape[1]].contiguous(
-                            memory_format=torch.channels_last)
-                else:
-                    dw = C.wgrad(xc, dpre, kh, kw, stride, pad)
-            cur.wait_stream(side)
-            dw.record_stream(cur)
-
-        # dgrad
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if is_stem:
-                raise NotImplementedError(
-                    'stem dgrad (3-channel input) is not needed: the image '
-                    'is a leaf tensor')
-            cin = xc.shape[1]
-            ones, zeros = _ones_zeros(cin, xc.device)
-            if stride == 1:
-                bf16_d = bf16 and dpre.shape[1] % 8 == 0
-                wpk_t = ctx.wpk_t  # packed by forward with wpk
-                if wpk_t is None:
-                    wpk_t = C.pack_weights(weight, True, bf16_d)
-                dsrc = dpre if bf16_d else dpre.float()
-                dx = C.conv_fwd(dsrc, wpk_t, ones, zeros, None, kh, kw, 1,
-                                pad, cin, ACT_CODE['Linear'])
-                if dx.dtype != xc.dtype:
-                    dx = dx.to(xc.dtype)
-            elif stride == 2 and kh == 2 and kw == 2 and pad == 0:
-                # k2/s2 windows don't overlap: each input pixel receives
-                # from exactly one output pixel, so dgrad decomposes into
-                # FOUR 1x1 convs (one per tap parity), scattered back into
-                # the interleaved input grid (the pool='Conv' downsampler).
-                dx = torch.empty_like(xc).contiguous(
-                    memory_format=torch.channels_last)
-                for r in range(2):
-                    for c in range(2):
-                        wt = weight[:, :, r:r + 1, c:c + 1]
-                        wpk_t = C.pack_weights(wt, True, bf16)
-                        part = C.conv_fwd(dpre, wpk_t, ones, zeros, None,
-                                          1, 1, 1, 0, cin,
-                                          ACT_CODE['Linear'])
-                        dx[:, :, r::2, c::2] = part
-            else:
-                raise NotImplementedError(
-                    f'HIP dgrad for k={kh} stride={stride} not implemented')
+        dx, dw = _conv_input_weight_grads(
+            C, xc, weight, dpre, kh, kw, stride, pad, bf16, is_stem,
+            stem_col, ctx.wpk_t, ctx.needs_input_grad[0],
+            ctx.needs_input_grad[1])
 
         return (dx, dw, dbias, dgamma, dbeta, None, None, dskip,
-                None, None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None,
+                ds_lin, None, None, dgamma_s, dbeta_s)
+
+
+class _ConvLinStatsFn(torch.autograd.Function):
+    """The front half of a training conv+BN on its own: s_lin = conv(x) +
+    bias and its batch statistics (running stats updated). The BN apply and
+    its backward belong to the consumer (_ConvBNActFn's dual form), which
+    hands back the gradient of s_lin; the backward here is wgrad + dgrad."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, rmean, rvar, kh, kw, stride, pad,
+                momentum, eps):
+        C = _C()
+        bf16 = _bf16_mode(x) and x.shape[1] % 8 == 0
+        dtype = torch.bfloat16 if bf16 else torch.float32
+        xc = x.to(dtype).contiguous(memory_format=torch.channels_last)
+        cout = weight.shape[0]
+        wpk_t = None
+        if stride == 1 and ctx.needs_input_grad[0]:
+            wpk, wpk_t = C.pack_weights_pair(weight, bf16,
+                                             bf16 and cout % 8 == 0)
+        else:
+            wpk = C.pack_weights(weight, False, bf16)
+        ones, zeros = _ones_zeros(cout, x.device)
+        bias_f = bias.float().contiguous() if bias is not None else zeros
+        s_lin, mean, rstd = _conv_lin_stats(
+            C, xc, wpk, ones, bias_f, kh, kw, stride, pad, cout, False,
+            bf16, rmean, rvar, momentum, eps)
+        ctx.meta = (kh, kw, stride, pad, bf16, bias is not None)
+        ctx.save_for_backward(xc, weight)
+        ctx.wpk_t = wpk_t
+        ctx.mark_non_differentiable(mean, rstd)
+        return s_lin, mean, rstd
+
+    @staticmethod
+    def backward(ctx, ds_lin, _dmean, _drstd):
+        kh, kw, stride, pad, bf16, has_bias = ctx.meta
+        xc, weight = ctx.saved_tensors
+        dbias = None
+        if has_bias and ctx.needs_input_grad[2]:
+            # a constant shift ahead of a train-mode BN has zero gradient
+            dbias = torch.zeros(ds_lin.shape[1], device=ds_lin.device,
+                                dtype=torch.float32)
+        dx, dw = _conv_input_weight_grads(
+            _C(), xc, weight, ds_lin, kh, kw, stride, pad, bf16, False,
+            False, ctx.wpk_t, ctx.needs_input_grad[0],
+            ctx.needs_input_grad[1])
+        return (dx, dw, dbias, None, None, None, None, None, None, None,
+                None)
 
 
 def _conv_infer_fp8(x, conv, bn, act_code, skip=None):
@@ -488,10 +601,47 @@ def conv_bn_act(x, conv, bn, act, act_module=None, training=False,
         kh, kw, stride, pad, act_code, use_bn, training,
         bn_momentum(bn, training) if use_bn else 0.1,
         bn.eps if use_bn else 1e-5,
-        is_stem)
+        is_stem, None, None, None, None, None)
     if act_module is not None:
         y = act_module(y)
     return y
+
+
+def dual_bn_applies(x, conv, bn, act, sx, sconv, sbn, training):
+    """Whether conv_bn_act_dual takes this Residual tail: both convs with
+    training-mode BN under autograd, a fusible activation, one compute dtype
+    on both sides. RTHD_BN_DUAL=0 turns the dual path off."""
+    if os.environ.get('RTHD_BN_DUAL') == '0':
+        return False
+    if not (training and torch.is_grad_enabled()):
+        return False
+    if bn is None or sbn is None or act not in ACT_CODE:
+        return False
+    if sconv.weight.shape[1] == 3 or conv.weight.shape[1] == 3:
+        return False
+    if sconv.stride[0] != 1 or conv.stride[0] != 1:
+        return False
+    return ((_bf16_mode(x) and x.shape[1] % 8 == 0) ==
+            (_bf16_mode(sx) and sx.shape[1] % 8 == 0))
+
+
+def conv_bn_act_dual(x, conv, bn, act, sx, sconv, sbn):
+    """act(bn(conv(x)) + bn_s(sconv(sx))) in training mode, the skip BN
+    applied inside the main BN's passes (dual_bn_applies must hold)."""
+    from .functional import bn_momentum
+    bump_train_stamp()
+    skh, skw = sconv.kernel_size
+    # the order of the separate path: skip conv and its stats first
+    s_lin, mean_s, rstd_s = _ConvLinStatsFn.apply(
+        sx, sconv.weight, sconv.bias, sbn.running_mean, sbn.running_var,
+        skh, skw, sconv.stride[0], sconv.padding[0],
+        bn_momentum(sbn, True), sbn.eps)
+    kh, kw = conv.kernel_size
+    return _ConvBNActFn.apply(
+        x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean,
+        bn.running_var, None, kh, kw, conv.stride[0], conv.padding[0],
+        ACT_CODE[act], True, True, bn_momentum(bn, True), bn.eps, False,
+        s_lin, mean_s, rstd_s, sbn.weight, sbn.bias)
 
 
 # ------------------------------------------------------------ elementwise --

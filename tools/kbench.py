@@ -1,10 +1,14 @@
 """Micro-benchmark individual HIP kernels (A/B timing + rocprof target).
 
-python tools/kbench.py [wgrad|conv|stem_wgrad|bn|nms|decode|all] [--iters N]
+python tools/kbench.py [wgrad|conv|halo_stats|stem_wgrad|bn|nms|decode|all]
+    [--iters N]
     [--variant row|tr|regt]   (wgrad only)
 Prints per-kernel ms and effective TFLOP/s on the flagship shapes; ``nms``
 prints the hard/soft batched NMS kernels against their eager twins,
-``decode`` the logits-in decode against the composition it replaces.
+``decode`` the logits-in decode against the composition it replaces;
+``halo_stats`` the halo conv with its BN-stats epilogue and the one-launch
+finish against the conv followed by bn_stats (the table behind
+ops.hip._HALO_STATS_MIN_TILES).
 """
 import argparse
 import os
@@ -123,6 +127,66 @@ def bench_conv(iters):
             except RuntimeError as e:
                 print(f'conv(64,sk={sk}) {name}: {e}')
                 break
+
+
+def bench_halo_stats(iters, rounds=3):
+    """Per 3x3 training-conv shape of the flagship step: the halo conv alone
+    (A), with its stats epilogue (B), B + bn_stats_from_parts (C), bn_stats
+    alone (D), and the two paths a layer chooses between: C against A + D
+    back to back. Medians of `rounds` interleaved rounds, us per call."""
+    import statistics
+    shapes = [
+        ('3x3 64->128 @256^2 B16', 16, 64, 128, 256),
+        ('3x3 128ch @256^2 B16', 16, 128, 128, 256),
+        ('3x3 128ch @128^2 B16', 16, 128, 128, 128),
+        ('3x3 128ch @64^2 B16', 16, 128, 128, 64),
+        ('3x3 128ch @32^2 B16', 16, 128, 128, 32),
+        ('3x3 128ch @16^2 B16', 16, 128, 128, 16),
+    ]
+    print('%-24s %6s %8s %8s %8s %8s %9s %7s' % (
+        'shape', 'tiles', 'halo', '+stats', '+finish', 'bn_stats',
+        'halo+bn', 'saved'))
+    for name, B, cin, cout, hw in shapes:
+        x = torch.randn(B, cin, hw, hw, device='cuda',
+                        dtype=torch.bfloat16).contiguous(memory_format=CL)
+        w = torch.randn(cout, cin, 3, 3, device='cuda') * 0.05
+        wpk = C.pack_weights(w, False, True)
+        ones = torch.ones(cout, device='cuda')
+        zeros = torch.zeros(cout, device='cuda')
+        rm = torch.zeros(cout, device='cuda')
+        rv = torch.ones(cout, device='cuda')
+        M = B * hw * hw
+        y = C.conv_fwd_halo(x, wpk, ones, zeros, None, 3, 3, 1, 1, cout, 0)
+
+        def halo():
+            return C.conv_fwd_halo(x, wpk, ones, zeros, None, 3, 3, 1, 1,
+                                   cout, 0)
+
+        def halo_s():
+            return C.conv_fwd_halo_stats(x, wpk, ones, zeros, 3, 3, 1, 1,
+                                         cout, 0)
+
+        def halo_sf():
+            o = halo_s()
+            return C.bn_stats_from_parts(o[1], o[2], rm, rv, 0.1, 1e-5, M)
+
+        def stats():
+            return C.bn_stats(y, rm, rv, 0.1, 1e-5)
+
+        def halo_bn():
+            return C.bn_stats(halo(), rm, rv, 0.1, 1e-5)
+
+        fns = (halo, halo_s, halo_sf, stats, halo_bn)
+        t = [[] for _ in fns]
+        for fn in fns:
+            timeit(fn, 5)
+        for _ in range(rounds):
+            for i, fn in enumerate(fns):
+                t[i].append(timeit(fn, iters, warmup=2) * 1e3)
+        m = [statistics.median(v) for v in t]
+        tiles = B * (hw // 8) * (hw // 16)
+        print('%-24s %6d %8.1f %8.1f %8.1f %8.1f %9.1f %7.1f' % (
+            name, tiles, m[0], m[1], m[2], m[3], m[4], m[4] - m[2]))
 
 
 def bench_fp8(iters):
@@ -339,6 +403,8 @@ if __name__ == '__main__':
         bench_wgrad(args.iters, args.variant)
     if args.which in ('conv', 'all'):
         bench_conv(args.iters)
+    if args.which in ('halo_stats', 'all'):
+        bench_halo_stats(args.iters)
     if args.which in ('fp8', 'all'):
         bench_fp8(args.iters)
     if args.which in ('stem', 'stem_wgrad', 'all'):
